@@ -2,20 +2,32 @@
 BASELINE.json config 2 workload (3-D KLE Laplacian, structured hex mesh
 [20,16,16], p=4 / ngl=5, ~1M DoF, Taylor-Green-3D Dirichlet data).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
       (N > 1: starts torch.distributed.run with N ranks itself)
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run does what the headline figure needs and no more: untimed setup
+(assembly, right-hand side, 40 iterations on a scratch vector that bring the
+device to its running clocks), the warm-up, the K timed steps, and the result
+line (value, ms_per_step, the in-region SpMV roofline).  --dump-outputs DIR
+writes what the timed path returned after its last step, the CG iterate x,
+to DIR/x.npy (float64; inputs are fixed and every kernel of a step sums in a
+fixed order, so two runs agree bit for bit and two builds compare array for
+array; for that the brick product's gather is a launch of its own here,
+--sr-gather 0, not folded into the CG update).  --full adds every other leg described below: the convergence solve,
+the per-kernel breakdown, the plain / per-rank / scalar-CSR SpMV legs, the
+operator chain, the streaming ceilings and the CPU baseline.
 
 A "step" is one CG iteration on the assembled device matrix (single-
 reduction CG + Jacobi: the fused vector update whose prologue applies the
 previous scalar stage, the SpMV, the (u, A u) partials; pipelined CG on N>1);
 the warm-up solve starts the recurrence and the K timed steps continue it
 (no restart inside the timed region), between barriers, max over ranks.  Assembly (device
-element kernels + gather) is untimed setup.  A full solve to rtol 1e-10 is
-run once for the convergence record.  The roofline uses HIP-event timings of
-the SpMV kernel inside the timed region and the algorithmic bytes of the
-node-block format; `traffic` comes from the rocprofv3 PMC pass recorded in
-profiles/ (or null).  cpu_baseline: the C oracle's CSR CG on the same
+element kernels + gather) is untimed setup.  The roofline uses HIP-event
+timings of the SpMV kernel inside the timed region and the algorithmic bytes
+of the node-block format; `traffic` comes from the rocprofv3 PMC pass recorded
+in profiles/ (or null).  With --full: a solve to rtol 1e-10 is run once for
+the convergence record, and cpu_baseline is the C oracle's CSR CG on the same
 matrix, OpenMP on the host cores, rank 0 at N=1 only.
 """
 import argparse
@@ -28,6 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DEVICE_WARM_ITS = 40    # plain runs: untimed iterations before the warm-up, in place of the convergence solve
 METRIC = "KLE CG iters/sec + SpMV GB/s (vs HBM roofline), 1M-DoF p=4 hex mesh"
 
 
@@ -36,6 +49,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: convergence solve, per-kernel breakdown, "
+                         "plain / per-rank / scalar-CSR SpMV, operator chain, streaming ceilings, CPU baseline "
+                         "(the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what they returned (the CG iterate x) to DIR/x.npy")
     ap.add_argument("--nelem", type=str, default="20,16,16")
     ap.add_argument("--ngl", type=int, default=5)
     ap.add_argument("--mesh", choices=["box", "unstructured"], default="box",
@@ -61,6 +80,10 @@ def parse():
                     help="auto: single-reduction CG on one GPU, pipelined CG (allreduce beside the SpMV) on N>1")
     ap.add_argument("--classic-cg", action="store_true",
                     help="two reductions per iteration instead of the single-reduction (Chronopoulos-Gear) CG")
+    ap.add_argument("--sr-gather", type=int, choices=[0, 1, 2], default=0,
+                    help="libkle's ksp_sr_gather: 0 (default here) the brick product's gather is a launch of its own "
+                         "(bitwise reproducible from run to run); 1 the library's default, 2 always: the CG update "
+                         "gathers it and takes (A u, u) from the bricks, summed in an order that varies between runs")
     ap.add_argument("--traffic", type=str, default=os.path.join(ROOT, "profiles", "traffic.json"))
     return ap.parse_args()
 
@@ -204,6 +227,15 @@ def main():
     ctx = pa.get_ctx()
     pa.runtime.set_row_padding(args.pad)
     pa.runtime.set_value_layout(args.layout)
+    # Same arguments, same outputs: the folded update (ksp_sr_gather 1, on in
+    # the library from 2^17 node rows) sums the bricks' (A u, u) shares in the
+    # order its waves happened to take their rows, and at config 2 its
+    # recurrence does not converge, so two runs' iterates drift apart (2.7e-3
+    # of max|x| after 300 steps, O(1) after 3000).  With the gather as its own
+    # launch every kernel of a step is bitwise reproducible, the iterate
+    # converges, and a step takes the same time (2,440 vs 2,421-2,441 it/s
+    # over 300 steps on one device).
+    pa.runtime.set_tuning("ksp_sr_gather", args.sr_gather)
     rank, nranks = ctx.rank, ctx.nranks
     nelem = [int(v) for v in args.nelem.split(",")]
     dim = len(nelem)
@@ -257,7 +289,7 @@ def main():
 
     # --- full solve to convergence (correctness record, untimed for the metric)
     solve = {}
-    if not args.no_solve:
+    if args.full and not args.no_solve:
         ksp = sol.getKSP()
         ksp.setType("pipecg" if (args.ksp == "pipecg" or (args.ksp == "auto" and nranks > 1)) else "cg")
         ksp.setTolerances(rtol=1e-10, atol=0.0, max_it=200000)
@@ -285,6 +317,15 @@ def main():
     kb.setOperators(K)
     kb.setUp()
     x = K.createVecRight()
+    if not args.full:
+        # the timed steps have always followed the convergence solve, which left
+        # the device at its running clocks (34 iterations at config 2); without
+        # that solve, as many iterations on a scratch vector keep `value` the
+        # figure it was (without them 20 steps read about 7 % lower)
+        xw = K.createVecRight()
+        kb.setFixedIterations(DEVICE_WARM_ITS)
+        kb.solve(b, xw)
+        del xw
     # the warm-up solve starts the recurrence (r = b, w = A u, first scalars);
     # the timed region continues it for exactly `steps` iterations
     kb.setFixedIterations(max(args.warmup, 1))
@@ -309,14 +350,19 @@ def main():
         raise SystemExit(f"bench: the timed CG recurrence diverged (reason {kb.getConvergedReason()}); "
                          f"use fewer --steps")
     spmv_cnt, spmv_ms = ctx.kernel_stats("spmv")
-    # per-kernel breakdown from a separate, untimed pass with every launch timed
-    nb_its = min(args.steps, 50)
-    ctx.set_profiling(True)
-    ctx.reset_stats()
-    kb.solveContinue(b, x, nb_its)
-    ctx.set_profiling(False)
-    brk = {k: ctx.kernel_stats(k)[1] / nb_its for k in ("spmv", "cg_update", "p_update", "reduce",
-                                                        "halo", "allreduce")}
+    if args.dump_outputs:
+        # x as the last timed step left it (before anything below continues the recurrence)
+        dump_outputs(args.dump_outputs, x.getArray(), rank, nranks, dist)
+    brk = None
+    if args.full:
+        # per-kernel breakdown from a separate, untimed pass with every launch timed
+        nb_its = min(args.steps, 50)
+        ctx.set_profiling(True)
+        ctx.reset_stats()
+        kb.solveContinue(b, x, nb_its)
+        ctx.set_profiling(False)
+        brk = {k: ctx.kernel_stats(k)[1] / nb_its for k in ("spmv", "cg_update", "p_update", "reduce",
+                                                            "halo", "allreduce")}
     t_max = t_loc
     # the timed products' algorithmic bytes (the bricks' own share where the CG
     # update gathers a split product; else K's, = the plain leg's)
@@ -358,41 +404,43 @@ def main():
 
     # plain SpMV leg: x = uniform[-1,1) from splitmix64 seeded
     # 0x5EED, 10 warm-ups, 200 timed repetitions of y = K x
-    lo, hi = K.getOwnershipRange()
-    xs = K.createVecRight()
-    xs.setArray(splitmix_uniform(0x5EED, lo, hi))
-    ys = K.createVecLeft()
-    for _ in range(10):
-        K.mult(xs, ys)
-    ctx.set_profiling(True, only="spmv")
-    ctx.reset_stats()
-    for _ in range(200):
-        K.mult(xs, ys)
-    pc_, pms = ctx.kernel_stats("spmv")
-    ctx.set_profiling(False)
-    # each rank's own part alone (no halo; ranks take turns, so ranks that
-    # share a GPU do not slow each other): the per-rank skew of N > 1
-    local_ms = None
-    if dist is not None:
-        for r in range(nranks):
+    spmv_plain, local_all = None, None
+    if args.full:
+        lo, hi = K.getOwnershipRange()
+        xs = K.createVecRight()
+        xs.setArray(splitmix_uniform(0x5EED, lo, hi))
+        ys = K.createVecLeft()
+        for _ in range(10):
+            K.mult(xs, ys)
+        ctx.set_profiling(True, only="spmv")
+        ctx.reset_stats()
+        for _ in range(200):
+            K.mult(xs, ys)
+        pc_, pms = ctx.kernel_stats("spmv")
+        ctx.set_profiling(False)
+        # each rank's own part alone (no halo; ranks take turns, so ranks that
+        # share a GPU do not slow each other): the per-rank skew of N > 1
+        local_ms = None
+        if dist is not None:
+            for r in range(nranks):
+                dist.barrier()
+                if r == rank:
+                    try:
+                        local_ms = K.timeLocalSpmv(xs, ys, 50)
+                    except pa.Error:  # (not a box-brick part)
+                        local_ms = None
             dist.barrier()
-            if r == rank:
-                try:
-                    local_ms = K.timeLocalSpmv(xs, ys, 50)
-                except pa.Error:  # (not a box-brick part)
-                    local_ms = None
-        dist.barrier()
-    local_all = [local_ms]
-    if dist is not None:
-        local_all = [None] * nranks
-        dist.all_gather_object(local_all, local_ms)
-    spmv_plain = {"kernel": spmv_kernel(K, args.layout, args.ngl), "reps": pc_, "avg_ms": pms / max(pc_, 1),
-                  "bytes": spmv_bytes_local,
-                  "gbps": spmv_bytes_local / (pms / max(pc_, 1) * 1e-3) / 1e9,
-                  "x": "uniform[-1,1) from splitmix64(0x5EED), global index order"}
+        local_all = [local_ms]
+        if dist is not None:
+            local_all = [None] * nranks
+            dist.all_gather_object(local_all, local_ms)
+        spmv_plain = {"kernel": spmv_kernel(K, args.layout, args.ngl), "reps": pc_, "avg_ms": pms / max(pc_, 1),
+                      "bytes": spmv_bytes_local,
+                      "gbps": spmv_bytes_local / (pms / max(pc_, 1) * 1e-3) / 1e9,
+                      "x": "uniform[-1,1) from splitmix64(0x5EED), global index order"}
 
     aij = None
-    if args.aij and nranks == 1:
+    if args.full and args.aij and nranks == 1:
         A = K.convert("aij")
         xa = A.createVecRight()
         ya = A.createVecLeft()
@@ -423,7 +471,7 @@ def main():
     traffic, traffic_status = lookup_traffic(args.traffic, tkey, kname, prod_bytes)
 
     ops = None
-    if args.ops == "on" or (args.ops == "auto" and nranks == 1):
+    if args.ops == "on" or (args.full and args.ops == "auto" and nranks == 1):
         try:
             ops = bench_operators(pa, mat, ctx, sol, dim)
         except pa.Error as e:
@@ -434,12 +482,13 @@ def main():
             ops = {"skipped": str(e)}
 
     cpu = None
-    if rank == 0 and nranks == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and nranks == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(K, b, args.cpu_seconds, args.cpu_threads)
 
     if rank == 0:
-        stream = ctx.stream_copy_gbps(1 << 30, 10)
-        stream_rd = ctx.stream_read_gbps(1 << 32, 10)
+        # (streaming ceilings: runs of their own, --full only; null otherwise)
+        stream = ctx.stream_copy_gbps(1 << 30, 10) if args.full else None
+        stream_rd = ctx.stream_read_gbps(1 << 32, 10) if args.full else None
         line = {
             "metric": METRIC,
             "value": iters_per_s,
@@ -448,6 +497,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": t_max / args.steps * 1e3,
+            "full": args.full,  # false: the legs beside the headline figure did not run (null below)
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -466,6 +516,7 @@ def main():
                        "ksp": ksp_type if ksp_type == "pipecg" else
                        ("cg" if args.classic_cg else "cg (single reduction, Chronopoulos-Gear)"),
                        "pc": "jacobi", "matrix_format": info["format"], "value_layout": "chunk16+tail" if args.layout == 1 else f"row streams padded to {args.pad}",
+                       "sr_gather": args.sr_gather,
                        "structured_columns": K.isStructured(),
                        "symmetric_storage": K.isSymmetricStorage(),
                        "parallelism": ((f"z-slab x{nranks}" if mesh_kind == "box" else
@@ -498,10 +549,10 @@ def main():
                          # 16-B nontemporal loads, 4 in flight per lane): what HBM
                          # delivers here, against the 8 TB/s peak
                          "achievable_gbps": stream_rd,
-                         "frac_of_achievable": achieved / (stream_rd * nranks) if achieved else None,
+                         "frac_of_achievable": achieved / (stream_rd * nranks) if achieved and stream_rd else None,
                          "read_ceiling_gbps": stream_rd,
                          "traffic_frac_of_read_ceiling": (traffic / (spmv_avg_max * 1e-3) / 1e9 / stream_rd
-                                                          if traffic and spmv_avg_max > 0 and nranks == 1
+                                                          if traffic and stream_rd and spmv_avg_max > 0 and nranks == 1
                                                           else None)},
             "cpu_baseline": cpu,
             "spmv_gbps": achieved,
@@ -521,6 +572,29 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, x_local, rank, nranks, dist):
+    """--dump-outputs: DIR/x.npy, the iterate the timed steps returned, float64
+    in global row order (ranks own consecutive row ranges; rank 0 writes).
+    Above 64 MB in all, a fixed sample: the sorted rows drawn without
+    replacement by numpy's default_rng(0)."""
+    import numpy as np
+    parts = [x_local]
+    if dist is not None:
+        parts = [None] * nranks
+        dist.all_gather_object(parts, x_local)
+    if rank != 0:
+        return
+    x = np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)
+    keep = DUMP_MAX_BYTES // x.itemsize
+    if x.size > keep:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, size=keep, replace=False))]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "x.npy"), x)
 
 
 def spmv_kernel(K, layout, ngl):

@@ -90,7 +90,7 @@ def test_comm_init_times_out_when_a_peer_never_joins():
 def test_bench_launches_its_own_ranks():
     env = dict(os.environ, KLE_TRANSPORT="host", KLE_DEVICE="0")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--nelem", "4,4,4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--nelem", "4,4,4",
                           "--ngl", "4", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -6,7 +6,7 @@
 #   tests:<pytest args>     GPU tests (one process, per-test timeout)
 #   ab:<json> [cg_ab args]  in-process CG A/B of tuning knobs (tools/cg_ab.py)
 #   spmv:<json> [args]      in-process SpMV A/B of tuning knobs (tools/spmv_ab.py)
-#   bench:<bench.py args>   one bench line -> $OUT/bench_<n>.json
+#   bench:<bench.py args>   one bench line -> $OUT/bench_<n>.json (pass --full for the legs beside the headline figure)
 #   prof:<bench.py args>    rocprofv3 kernel trace + stats of a bench run
 #   pmc:<bench.py args>     PMC FETCH_SIZE and WRITE_SIZE passes (separate runs)
 #   sprof:<spmv_ab.py args> rocprofv3 kernel trace + stats of an in-process SpMV A/B
