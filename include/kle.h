@@ -177,6 +177,10 @@ int kle_ctx_barrier(kle_ctx *ctx); /* device-side RCCL barrier + stream sync */
  * (may be NULL) and the transport: 0 single rank, 1 RCCL, 2 host-staged,
  * 3 IPC mailboxes (kle_ctx_enable_ipc). */
 int kle_ctx_get_device(kle_ctx *ctx, int *device, char *pci_bus_id, int len, int *transport);
+/* The context's HIP stream (a hipStream_t), on which all device work is
+ * ordered: for events recorded around library calls (tools/elem_ab.py) and
+ * for interop.  No reference counterpart. */
+int kle_ctx_get_stream(kle_ctx *ctx, void **stream);
 /* What the RCCL communicator itself reports (ncclCommCount /
  * ncclCommUserRank; the MPI communicator of DMPlex.distribute, dmplex.py:21,
  * and of KSPSolve's reductions, kle_solver.py:35): *count = 0, *rank = -1
@@ -354,6 +358,32 @@ int kle_assemble_ns(kle_ctx *ctx, kle_mesh *m, kle_mat **K, kle_mat **Krhs, kle_
  * the full node adjacency (pattern 3), explicit zeros kept as PETSc does. */
 int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **SrT, kle_mat **DivSrT);
 
+/* Element-wise operator of a uniform box mesh: y = A x formed from the one
+ * element matrix of the mesh, no assembled values.  which: 0 K (free rows x
+ * free columns + unit Dirichlet diagonal), 1 Krhs (free rows x Dirichlet
+ * columns, negated, + unit Dirichlet diagonal): the same operators
+ * kle_assemble_kle assembles (MatFS.buildFS, mat_fs.py:150-190).
+ * kle_mesh_create_box makes every element the same brick, so K u = sum_e
+ * S_e^T K_e0 S_e u with K_e0 the first local element's matrix (from the
+ * assembly's own element kernel): one FP64 MFMA GEMM K_e0 x [gathered element
+ * vectors] and a gather per node in ascending element order -- bitwise
+ * repeatable, and equal to the assembled product to rounding plus the spread
+ * of the element matrices over the mesh (coordinate rounding, ~1e-15).
+ * Memory: K_e0, the connectivity and incidence tables, one Dirichlet flag per
+ * node and E * dim * ngl^dim doubles of element results; nothing of nnz(K).
+ * The result is a kle_mat of format 2 ("elem").  It supports kle_mat_mult,
+ * kle_mat_mult_add, kle_mat_get_diagonal, the size / local-size / ownership
+ * getters, kle_mat_get_info (nz_used = 0: no entry is stored),
+ * kle_mat_spmv_bytes, kle_mat_spmv_kernel, kle_mat_destroy and
+ * kle_ksp_set_operators with cg (classic and single reduction: the generic
+ * paths) or gmres and PC none or jacobi.  Calls that need stored
+ * values return KLE_ERR_SUP: set_values, assemble, axpy, diagonal_scale,
+ * get_row, get_csr, get_csr_size, convert_aij, duplicate, set_symmetric,
+ * move_values, time_local_spmv, PC lu.
+ * Needs a box mesh with its Dirichlet set, 2-D or 3-D, on one rank;
+ * KLE_ERR_SUP for unstructured meshes, no-slip meshes and nranks > 1. */
+int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+
 /* Generic AIJ (petsc4py Mat().createAIJ + setValues + assemble). */
 int kle_mat_create_aij(kle_ctx *ctx, int64_t m_local, int64_t n_local, int64_t m_global,
                        int64_t n_global, const int32_t *d_nnz, const int32_t *o_nnz,
@@ -373,11 +403,12 @@ int kle_mat_get_ownership_range(const kle_mat *A, int64_t *lo, int64_t *hi);
 int kle_mat_get_local_size(const kle_mat *A, int64_t *m_local, int64_t *n_local);
 int kle_mat_get_local_nnz(const kle_mat *A, int64_t *nnz);
 /* MatGetInfo (+ sizes): PETSc nonzeros of the owned rows, the storage format
- * (0 node-block, 1 scalar AIJ), block shape and the SpMV's algorithmic bytes. */
+ * (0 node-block, 1 scalar AIJ, 2 element-wise: nz_used 0), block shape and
+ * the SpMV's algorithmic bytes. */
 typedef struct {
     int64_t m_global, n_global, m_local, n_local;
     int64_t nz_used;       /* PETSc nonzeros of the owned rows (explicit zeros included) */
-    int format;            /* 0 node-block CSR, 1 scalar AIJ */
+    int format;            /* 0 node-block CSR, 1 scalar AIJ, 2 element-wise */
     int block_rows, block_cols;
     double spmv_bytes;     /* algorithmic bytes of one y = A x on this rank */
 } kle_mat_info;
@@ -445,7 +476,7 @@ int kle_get_nb_pad(void);
  * per-stream padding). */
 int kle_set_nb_layout(int layout);
 int kle_get_nb_layout(void);
-/* "nb" (node-block) or "aij". */
+/* "nb" (node-block), "aij" or "elem" (kle_mat_create_kle_element). */
 int kle_mat_get_format(const kle_mat *A, char *buf, int buflen);
 /* Bytes one SpMV with this matrix moves (algorithmic: matrix + x + y). */
 int kle_mat_spmv_bytes(const kle_mat *A, double *bytes);

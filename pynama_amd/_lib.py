@@ -62,7 +62,8 @@ _SIGS = {
     "kle_ctx_synchronize": [vp],
     "kle_ctx_barrier": [vp],
     "kle_ctx_get_device": [vp, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int)],
-    "kle_ctx_get_comm_info": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "kle_ctx_get_stream": [vp, pvp],
+    "kle_ctx_get_comm_info":[vp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "kle_brick_plan_box": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                            C.POINTER(C.c_double)],
     "kle_ctx_enable_ipc": [vp],
@@ -123,6 +124,7 @@ _SIGS = {
     "kle_element_kle": [vp, vp, C.c_int64, f64p, f64p],
     "kle_assemble_operators": [vp, vp, pvp, pvp, pvp],
     "kle_assemble_ns": [vp, vp] + [pvp] * 9,
+    "kle_mat_create_kle_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_aij": [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, pvp],
     "kle_mat_create_aij_csr": [vp, C.c_int64, C.c_int64, i64p, i64p, f64p, pvp],
     "kle_mat_set_values": [vp, C.c_int32, i64p, C.c_int32, i64p, f64p, C.c_int],

@@ -1210,14 +1210,17 @@ struct ElemSetup {
     }
 };
 
-static int element_setup(kle_ctx *ctx, const kle_mesh *m, ElemSetup &S)
+// (nel_limit >= 0: the leading nel_limit local elements only)
+static int element_setup(kle_ctx *ctx, const kle_mesh *m, ElemSetup &S, int64_t nel_limit = -1)
 {
     const int dim = m->dim, nc = 1 << dim, G1 = 1 + dim * dim;
-    const int64_t nel = m->elem_end - m->elem_begin;
+    const int64_t nel_all = m->elem_end - m->elem_begin;
+    const int64_t nel = nel_limit >= 0 ? std::min(nel_limit, nel_all) : nel_all;
     S.nel = nel;
     KLE_TRY(upload_tables(ctx, m->ngl, S.T));
-    std::vector<double> corners(std::max<int64_t>(nel * nc * dim, 1));
+    std::vector<double> corners(std::max<int64_t>(nel_all * nc * dim, 1));
     KLE_TRY(kle_mesh_get_corners(m, corners.data()));
+    corners.resize(std::max<int64_t>(nel * nc * dim, 1));
     S.nqF = dim == 2 ? S.T.F.np1 * S.T.F.np1 : S.T.F.np1 * S.T.F.np1 * S.T.F.np1;
     S.nqR = dim == 2 ? S.T.R.np1 * S.T.R.np1 : S.T.R.np1 * S.T.R.np1 * S.T.R.np1;
     KLE_HIP(hipMalloc(&S.dX, sizeof(double) * corners.size()));
@@ -1292,6 +1295,34 @@ static int element_matrices(kle_ctx *ctx, const kle_mesh *m, double **dKe, doubl
     return 0;
 }
 
+// K_e of the first local element alone, as blocks [l][m][a][b] in a new device
+// buffer: the geometry and element kernels of the assembly on that element's
+// own corners, so the values are the ones the assembled K received from it
+// (the element-wise operator, kle_elem.hip).
+int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe)
+{
+    const int dim = m->dim, ne = m->nn(), dw = dim == 2 ? 1 : 3;
+    ElemSetup S;
+    KLE_TRY(element_setup(ctx, m, S, 1));
+    if (S.nel != 1) return fail(KLE_ERR_ARG, "the mesh has no local element");
+    double *dRwe = nullptr;
+    *dKe = nullptr;
+    if (hipMalloc(dKe, sizeof(double) * (size_t)ne * ne * dim * dim) != hipSuccess ||
+        hipMalloc(&dRwe, sizeof(double) * (size_t)ne * ne * dim * dw) != hipSuccess) {
+        (void)hipGetLastError();
+        if (*dKe) hipFree(*dKe);
+        *dKe = nullptr;
+        return fail(KLE_ERR_MEM, "element matrix does not fit");
+    }
+    int rc = element_batch(ctx, m, S, 0, 1, *dKe, dRwe, nullptr);
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(KLE_ERR_DEVICE, "element kernel failed");
+    hipFree(dRwe);
+    if (rc) {
+        hipFree(*dKe);
+        *dKe = nullptr;
+    }
+    return rc;
+}
 
 // ---------------------------------------------------------------- operators
 // Operators (mat_fs.py:194-271, spectral.py:162-228) are collocation operators

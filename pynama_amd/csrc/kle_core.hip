@@ -1089,6 +1089,13 @@ int kle_ctx_get_device(kle_ctx *c, int *device, char *pci_bus_id, int len, int *
     return 0;
 }
 
+int kle_ctx_get_stream(kle_ctx *c, void **stream)
+{
+    KLE_ARG(c && stream, "bad arg");
+    *stream = (void *)c->stream;
+    return 0;
+}
+
 int kle_ctx_get_comm_info(kle_ctx *c, int *count, int *rank)
 {
     KLE_ARG(c && count && rank, "bad arg");

@@ -1,0 +1,431 @@
+// kle_elem.hip -- element-wise K and Krhs of a uniform box mesh (kle_mat kind 2).
+//
+// kle_mesh_create_box makes every element the same brick, so every element
+// matrix equals that of the first element up to coordinate rounding and
+//
+//     K u = sum over elements e of  S_e^T  K_e0  S_e u
+//
+// with the Dirichlet masking of MatFS.buildFS (mat_fs.py:150-190): no matrix
+// values are stored or streamed.  K_e0 (nd x nd, nd = dim * ngl^dim) stays in
+// cache; the product is one FP64 GEMM K_e0 [nd x nd] * X [nd x E] followed by
+// a gather per node.
+//
+//   k_elem_gemm    one 256-thread workgroup per (batch of 16 * NCT elements,
+//                  NCT = 2 or 1; group of 128 rows).  The batch's x entries
+//                  are gathered through the connectivity into LDS, 64 k rows
+//                  at a time, masked by selection (K: Dirichlet entries
+//                  dropped; Krhs: free entries dropped; the rule is folded
+//                  into the connectivity as -1), so an Inf or NaN in a masked
+//                  entry is never read.  Every wave owns two 16-row tiles and
+//                  keeps 2 * NCT accumulators; per k step of 4 it feeds each
+//                  of its two K_e0 operands (stored in operand order: one
+//                  coalesced 512-B load each) to NCT v_mfma_f64_16x16x4_f64
+//                  (lane: A[l = lane&15][k = lane>>4], B[k = lane>>4][n =
+//                  lane&15]; result reg r at l = (lane>>4) + 4r, n = lane&15).
+//                  Loads run a chunk (operands, x) or two (node ids) ahead of
+//                  the MFMAs in registers.  Rows and columns beyond nd and
+//                  elements beyond E are zero operands and are never stored.
+//                  Krhs negates the result (the assembly adds -K_e).
+//   k_elem_gather  one thread per owned DoF: the sum of its node's incidence
+//                  entries from the element results in table (ascending
+//                  element) order -- fixed order, no atomics, bitwise
+//                  repeatable.  Dirichlet rows: y_i = x_i (both operators).
+#include <algorithm>
+#include <cstring>
+
+#include "kle_internal.hpp"
+
+namespace kle {
+
+struct ElemOp {
+    int which = 0, dim = 3, nn = 0, nd = 0, ndp = 0, maxinc = 8, nct = 1;
+    int64_t E = 0, N = 0;
+    double *d_kt = nullptr;     // K_e0 padded to ndp x ndp in MFMA operand order [row tile][k step][lane]
+    double *d_kdiag = nullptr;  // [nd] its diagonal
+    double *d_ws = nullptr;     // [E][nd] element results
+    int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order; -1 where the operator drops the entry
+    int32_t *d_inc = nullptr;   // [N][maxinc] node -> e * nn + l, ascending e, -1 padded
+    uint8_t *d_dir = nullptr;   // [N] Dirichlet flag
+};
+
+constexpr int EG_KC = 64;            // k rows of X per LDS chunk
+constexpr int EG_TR = 2;             // 16-row tiles per wave
+constexpr int EG_ROWS = 4 * EG_TR * 16;  // rows per workgroup
+
+typedef double edbl4 __attribute__((ext_vector_type(4)));
+
+template <int DIM, int NCT>
+__global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int64_t E,
+                                                      const double *__restrict__ kt,
+                                                      const int32_t *__restrict__ mconn,
+                                                      const double *__restrict__ x, double *__restrict__ ws,
+                                                      const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    constexpr int NE = 16 * NCT, SX = NE + 1;  // (odd row stride: the fill's lanes run along k)
+    constexpr int NPT = EG_KC * NE / 256;      // x entries per thread and chunk: k row `lane`, elements wv + 4 i
+    constexpr int KS = EG_KC / 4;              // k steps per chunk
+    __shared__ double sX[EG_KC * SX];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int64_t e0 = (int64_t)blockIdx.x * NE;
+    const int rt0 = ((int)blockIdx.y * 4 + wv) * EG_TR;  // this wave's first row tile
+    const int ntile = ndp >> 4, nks = ndp >> 2;
+
+    const edbl4 z4 = {0.0, 0.0, 0.0, 0.0};
+    edbl4 acc[EG_TR][NCT];
+#pragma unroll
+    for (int j = 0; j < EG_TR; ++j)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) acc[j][c] = z4;
+
+    // Three loads deep: while chunk c runs its MFMAs, the x entries and the
+    // K_e0 operands of chunk c + 1 and the node ids of chunk c + 2 are in
+    // flight.  Node ids come through the masked connectivity (-1: dropped --
+    // selection, the entry is never read; also beyond nd, E and the last chunk).
+    int nr[NPT];
+    double xr[NPT], ar[EG_TR][KS], an[EG_TR][KS];
+    auto fetch_idx = [&](int k0) {
+        const int g = k0 + lane;
+        const int l = g / DIM;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const int64_t e = e0 + wv + 4 * i;
+            nr[i] = g < nd && e < E ? mconn[e * nn + l] : -1;
+        }
+    };
+    auto fetch_x = [&](int k0) {
+        const int g = k0 + lane;
+        const int a = g - (g / DIM) * DIM;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) xr[i] = nr[i] >= 0 ? x[(int64_t)nr[i] * DIM + a] : 0.0;
+    };
+    // (a tile beyond the last re-reads the wave's first: its sums are never stored)
+    auto fetch_a = [&](int k0, double (&t)[EG_TR][KS]) {
+        const int nksc = max(min(EG_KC, ndp - k0), 0) >> 2;
+        if (rt0 >= ntile) return;
+#pragma unroll
+        for (int j = 0; j < EG_TR; ++j) {
+            const double *ka = kt + ((int64_t)(rt0 + j < ntile ? rt0 + j : rt0) * nks + (k0 >> 2)) * 64 + lane;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) t[j][ks] = ks < nksc ? ka[ks * 64] : 0.0;
+        }
+    };
+    fetch_idx(0);
+    fetch_a(0, ar);
+    fetch_x(0);
+    fetch_idx(EG_KC);
+    for (int k0 = 0; k0 < ndp; k0 += EG_KC) {
+        const int nksc = min(EG_KC, ndp - k0) >> 2;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) sX[lane * SX + wv + 4 * i] = xr[i];
+        __syncthreads();
+        fetch_x(k0 + EG_KC);
+        fetch_idx(k0 + 2 * EG_KC);
+        fetch_a(k0 + EG_KC, an);
+        if (rt0 < ntile) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks < nksc) {
+#pragma unroll
+                    for (int c = 0; c < NCT; ++c) {
+                        const double b = sX[(ks * 4 + kq) * SX + c * 16 + li];
+#pragma unroll
+                        for (int j = 0; j < EG_TR; ++j)
+                            acc[j][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[j][ks], b, acc[j][c], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < EG_TR; ++j)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) ar[j][ks] = an[j][ks];
+    }
+#pragma unroll
+    for (int j = 0; j < EG_TR; ++j)
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) {
+            const int64_t e = e0 + c * 16 + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int l = (rt0 + j) * 16 + kq + 4 * r;
+                if (rt0 + j < ntile && l < nd && e < E) ws[e * nd + l] = negate ? -acc[j][c][r] : acc[j][c][r];
+            }
+        }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_elem_gather(int64_t N, int nn, int nd, int maxinc,
+                                                     const int32_t *__restrict__ inc,
+                                                     const uint8_t *__restrict__ dir,
+                                                     const double *__restrict__ ws, const double *__restrict__ x,
+                                                     double *__restrict__ y, const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    if (dir[node]) {
+        y[i] = x[i];  // setIndices2One: unit Dirichlet diagonal of K and of Krhs
+        return;
+    }
+    double s = 0.0;
+    for (int j = 0; j < maxinc; ++j) {
+        const int t = inc[node * maxinc + j];
+        if (t < 0) break;
+        const int e = t / nn, l = t - e * nn;
+        s += ws[(int64_t)e * nd + l * DIM + a];
+    }
+    y[i] = s;
+}
+
+// diagonal: the incident elements' K_e0 diagonal entries in the same order
+// (K), 0 (Krhs: a free row holds Dirichlet columns only); 1 on Dirichlet rows
+template <int DIM>
+__global__ __launch_bounds__(256) void k_elem_diag(int64_t N, int nn, int maxinc, int which,
+                                                   const int32_t *__restrict__ inc,
+                                                   const uint8_t *__restrict__ dir,
+                                                   const double *__restrict__ kdiag, double *__restrict__ d)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    if (dir[node]) {
+        d[i] = 1.0;
+        return;
+    }
+    double s = 0.0;
+    if (which == 0)
+        for (int j = 0; j < maxinc; ++j) {
+            const int t = inc[node * maxinc + j];
+            if (t < 0) break;
+            s += kdiag[(t % nn) * DIM + a];
+        }
+    d[i] = s;
+}
+
+// Every index the device tables hold, checked on the host before upload: a
+// bad table is an error code, never an out-of-range access.
+static int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E,
+                         int nn, int maxinc)
+{
+    if ((int64_t)conn.size() != E * nn || (int64_t)inc.size() != N * maxinc)
+        return fail(KLE_ERR_SIZ, "element operator: table sizes do not match the mesh");
+    for (int64_t k = 0; k < E * nn; ++k)
+        if (conn[k] < 0 || conn[k] >= N)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld = %d outside [0, %lld)",
+                        (long long)k, conn[k], (long long)N);
+    for (int64_t i = 0; i < N; ++i) {
+        bool ended = false;
+        int32_t prev = -1;
+        for (int j = 0; j < maxinc; ++j) {
+            const int32_t t = inc[i * maxinc + j];
+            if (t < 0) {
+                if (t != -1 || j == 0)
+                    return fail(KLE_ERR_OUTOFRANGE, "element operator: node %lld has a bad incidence entry", (long long)i);
+                ended = true;
+                continue;
+            }
+            if (ended || (int64_t)t >= E * nn || conn[t] != i || (prev >= 0 && t / nn <= prev / nn))
+                return fail(KLE_ERR_OUTOFRANGE, "element operator: incidence entry %d of node %lld is inconsistent", j,
+                            (long long)i);
+            prev = t;
+        }
+    }
+    return 0;
+}
+
+template <int DIM>
+static void launch_gemm(const ElemOp *P, dim3 grid, hipStream_t st, const double *x, const int *istate)
+{
+#define KLE_ELEM_GEMM(NCT)                                                                                   \
+    hipLaunchKernelGGL((k_elem_gemm<DIM, NCT>), grid, dim3(256), 0, st, P->which, P->nn, P->nd, P->ndp, P->E, \
+                       P->d_kt, P->d_conn, x, P->d_ws, istate)
+    if (P->nct == 2) KLE_ELEM_GEMM(2);
+    else KLE_ELEM_GEMM(1);
+#undef KLE_ELEM_GEMM
+}
+
+int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
+{
+    const ElemOp *P = A->elem;
+    if (!P) return fail(KLE_ERR_STATE, "element operator without tables");
+    if (x->n_local != A->n_local || y->n_local != A->m_local || x->ghost_lo || x->ghost_hi)
+        return fail(KLE_ERR_SIZ, "element operator: vector layout does not match");
+    if (x->d == y->d) return fail(KLE_ERR_ARG, "element operator: y must not alias x");
+    hipStream_t st = A->ctx->stream;
+    const int ne = 16 * P->nct;
+    dim3 grid((unsigned)((P->E + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS));
+    if (P->dim == 2) launch_gemm<2>(P, grid, st, x->d, istate);
+    else launch_gemm<3>(P, grid, st, x->d, istate);
+    KLE_HIP(hipGetLastError());
+    const int64_t n = P->N * P->dim;
+    dim3 gg((unsigned)((n + 255) / 256));
+    if (P->dim == 2)
+        hipLaunchKernelGGL(k_elem_gather<2>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->d_inc, P->d_dir,
+                           P->d_ws, x->d, y->d, istate);
+    else
+        hipLaunchKernelGGL(k_elem_gather<3>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->d_inc, P->d_dir,
+                           P->d_ws, x->d, y->d, istate);
+    KLE_HIP(hipGetLastError());
+    return 0;
+}
+
+int elem_diagonal(const kle_mat *A, kle_vec *d)
+{
+    const ElemOp *P = A->elem;
+    if (!P) return fail(KLE_ERR_STATE, "element operator without tables");
+    hipStream_t st = A->ctx->stream;
+    const int64_t n = P->N * P->dim;
+    dim3 gg((unsigned)((n + 255) / 256));
+    if (P->dim == 2)
+        hipLaunchKernelGGL(k_elem_diag<2>, gg, dim3(256), 0, st, P->N, P->nn, P->maxinc, P->which, P->d_inc, P->d_dir,
+                           P->d_kdiag, d->d);
+    else
+        hipLaunchKernelGGL(k_elem_diag<3>, gg, dim3(256), 0, st, P->N, P->nn, P->maxinc, P->which, P->d_inc, P->d_dir,
+                           P->d_kdiag, d->d);
+    KLE_HIP(hipGetLastError());
+    KLE_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+void elem_drop(kle_mat *A)
+{
+    ElemOp *P = A->elem;
+    if (!P) return;
+    (void)hipFree(P->d_kt);
+    (void)hipFree(P->d_kdiag);
+    (void)hipFree(P->d_ws);
+    (void)hipFree(P->d_conn);
+    (void)hipFree(P->d_inc);
+    (void)hipFree(P->d_dir);
+    delete P;
+    A->elem = nullptr;
+}
+
+// Algorithmic bytes of one product: element matrix, connectivity, incidence
+// and Dirichlet tables, x read, y written, the element results written and read.
+double elem_spmv_bytes(const kle_mat *A)
+{
+    const ElemOp *P = A->elem;
+    if (!P) return 0.0;
+    return 8.0 * P->nd * P->nd + 4.0 * P->E * P->nn + 4.0 * P->N * P->maxinc + 1.0 * P->N +
+           8.0 * A->n_local + 8.0 * A->m_local + 2.0 * 8.0 * P->E * P->nd;
+}
+
+std::string elem_kernel_name(const kle_mat *A)
+{
+    const ElemOp *P = A->elem;
+    if (!P) return "?";
+    const std::string d = std::to_string(P->dim);
+    return "k_elem_gemm<" + d + "," + std::to_string(P->nct) + ">+k_elem_gather<" + d + ">";
+}
+
+}  // namespace kle
+
+using namespace kle;
+
+extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which == 0 || which == 1, "which must be 0 (K) or 1 (Krhs)");
+    if (m->kind != 0) return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
+    if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "element-wise operator: no-slip meshes are not supported");
+    if (m->nranks > 1 || ctx->nranks > 1)
+        return fail(KLE_ERR_SUP, "element-wise operator: one rank only (%d ranks)", std::max(m->nranks, ctx->nranks));
+    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+    const int dim = m->dim, nn = m->nn(), nd = dim * nn, ndp = (nd + 15) & ~15, maxinc = 1 << dim;
+    const int64_t E = m->elem_end - m->elem_begin, N = m->node_end - m->node_begin;
+    KLE_ARG(E >= 1 && N >= 1 && m->ext_begin == 0 && m->node_begin == 0 && m->ext_end == N, "unexpected one-rank layout");
+    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
+    if ((int64_t)m->dir.size() != N) return fail(KLE_ERR_SIZ, "element operator: Dirichlet flags do not match the mesh");
+
+    // tables (host), validated before upload
+    std::vector<int64_t> conn64((size_t)E * nn);
+    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
+    std::vector<int32_t> conn((size_t)E * nn), inc((size_t)N * maxinc, -1);
+    std::vector<uint8_t> cnt((size_t)N, 0);
+    for (int64_t k = 0; k < E * nn; ++k) {
+        const int64_t g = conn64[k];
+        if (g < 0 || g >= N)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld outside the mesh", (long long)k);
+        conn[k] = (int32_t)g;
+        if (cnt[g] >= maxinc)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: node %lld lies in more than %d elements", (long long)g, maxinc);
+        inc[g * maxinc + cnt[g]++] = (int32_t)k;  // k = e * nn + l, ascending e
+    }
+    KLE_TRY(elem_validate(conn, inc, N, E, nn, maxinc));
+    // the mask rule folded into the connectivity the GEMM reads: K drops the
+    // Dirichlet entries of x, Krhs the free ones
+    for (int64_t k = 0; k < E * nn; ++k)
+        if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
+
+    KLE_HIP(hipSetDevice(ctx->device));
+    // K_e0 through the assembly's own geometry and element kernels
+    double *dKe = nullptr;
+    KLE_TRY(element_first_k(ctx, m, &dKe));
+    std::vector<double> kb((size_t)nd * nd);
+    hipError_t he = hipMemcpy(kb.data(), dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(dKe);
+    if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element matrix download failed: %s", hipGetErrorString(he));
+    // blocks [l][m][a][b] -> K[l dim + a][m dim + b], zero-padded to ndp, in operand order
+    auto kat = [&](int r, int c) {
+        return kb[(((size_t)(r / dim) * nn + c / dim) * dim + r % dim) * dim + c % dim];
+    };
+    std::vector<double> kt((size_t)ndp * ndp, 0.0), kdiag((size_t)nd);
+    const int nks = ndp / 4;
+    for (int rt = 0; rt < ndp / 16; ++rt)
+        for (int ks = 0; ks < nks; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int r = rt * 16 + (lane & 15), c = ks * 4 + (lane >> 4);
+                if (r < nd && c < nd) kt[((size_t)rt * nks + ks) * 64 + lane] = kat(r, c);
+            }
+    for (int r = 0; r < nd; ++r) kdiag[r] = kat(r, r);
+
+    kle_mat *A = new kle_mat;
+    ElemOp *P = new ElemOp;
+    A->ctx = ctx;
+    A->kind = 2;
+    A->elem = P;
+    A->R = A->C = dim;
+    A->nrows = N;
+    A->m_global = A->n_global = A->m_local = A->n_local = N * dim;
+    P->which = which;
+    P->dim = dim;
+    P->nn = nn;
+    P->nd = nd;
+    P->ndp = ndp;
+    P->maxinc = maxinc;
+    P->E = E;
+    P->N = N;
+    // element columns per held K_e0 operand: two tiles of 16 where that still
+    // gives every CU a workgroup, else one (four would spill the operand
+    // double buffer out of 256 VGPRs)
+    const int64_t nrg = (ndp + EG_ROWS - 1) / EG_ROWS;
+    P->nct = (E + 31) / 32 * nrg >= ctx->num_cus ? 2 : 1;
+    auto up = [&](auto **dp, const void *src, size_t bytes) {
+        if (hipMalloc(dp, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *dp = nullptr;
+            return fail(KLE_ERR_MEM, "out of device memory for the element-wise operator");
+        }
+        return src ? h2d(*dp, src, bytes) : 0;
+    };
+    int rc = up(&P->d_kt, kt.data(), sizeof(double) * kt.size());
+    if (!rc) rc = up(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
+    if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
+    if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);
+    if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nd);
+    if (rc) {
+        kle_mat_destroy(A);
+        return rc;
+    }
+    *out = A;
+    return 0;
+}

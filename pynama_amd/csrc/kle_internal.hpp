@@ -194,9 +194,14 @@ struct kle_vec {
     bool owns = true;
 };
 
+namespace kle {
+struct ElemOp;  // kle_elem.hip: the element-wise operator of a uniform box mesh
+}
+
 struct kle_mat {
     kle_ctx *ctx = nullptr;
-    int kind = 0;  // 0 node-block, 1 scalar AIJ
+    int kind = 0;  // 0 node-block, 1 scalar AIJ, 2 element-wise (no stored values: elem)
+    kle::ElemOp *elem = nullptr;  // kind 2
     int halo_overlap = 1;          // N>1: interior rows run while the halo is in flight
     int64_t int_lo = 0, int_hi = 0;  // rows [int_lo, int_hi) read no ghost entries
     int64_t row_lat[3] = {1, 1, 1};  // lattice of the owned rows (x, y, z extents)
@@ -398,6 +403,19 @@ int halo_reverse(kle_ctx *ctx, const double *send_hi, int64_t n_send, int hi_ran
                  int lo_rank, hipStream_t st);  // kle_core.hip
 int halo_reverse_plan(kle_ctx *ctx, const HaloPlan &P, int64_t hi0, int bs, const double *gsend, double *rbuf,
                       hipStream_t st);  // kle_core.hip
+// element-wise operator (kle_elem.hip; kle_mat kind 2)
+int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe);  // kle_assemble.hip
+int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+int elem_diagonal(const kle_mat *A, kle_vec *d);
+void elem_drop(kle_mat *A);
+double elem_spmv_bytes(const kle_mat *A);
+std::string elem_kernel_name(const kle_mat *A);
+// kind 2 holds no assembled values: the calls that need them end here
+#define KLE_NO_ELEM(A, what)                                                                              \
+    do {                                                                                                  \
+        if ((A) && (A)->kind == 2)                                                                        \
+            return kle::fail(KLE_ERR_SUP, "%s: an element-wise operator holds no assembled values", what); \
+    } while (0)
 std::string sym_kernel_name(const kle_mat *A);
 double sym_spmv_bytes(const kle_mat *A);
 double brick_split_bytes(const kle_mat *A);  // a split brick product: the bricks alone

@@ -1794,6 +1794,7 @@ static int lu_factor(kle_ksp *k)
 {
     kle_ctx *c = k->ctx;
     kle_mat *A = k->A;
+    KLE_NO_ELEM(A, "PC lu");
     if (c->nranks > 1)
         return fail(KLE_ERR_SUP, "PC lu on %d ranks needs a parallel direct solver (PETSc: MUMPS / SuperLU_dist); "
                                  "use -ksp_type cg -pc_type jacobi (K is SPD)", c->nranks);
@@ -1933,6 +1934,7 @@ int kle_ksp_set_up(kle_ksp *k)
 {
     KLE_ARG(k && k->A, "operators not set");
     if (k->setup) return 0;
+    if (k->pc == "lu") KLE_NO_ELEM(k->A, "PC lu");
     free_work(k);
     if (k->pc == "lu") {
         KLE_TRY(make_vec_like_cols(k, &k->p));

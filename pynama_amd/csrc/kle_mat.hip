@@ -758,6 +758,12 @@ int spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
 {
     kle_ctx *c = A->ctx;
     std::pair<hipEvent_t, hipEvent_t> ev;
+    if (A->kind == 2) {
+        KLE_TRY(c->tic("spmv", &ev));
+        KLE_TRY(elem_spmv(A, x, y, istate));
+        KLE_TRY(c->toc("spmv", &ev));
+        return 0;
+    }
     if (A->kind == 0 && A->d_sval && g_tune.spmv_sym) {
         // symmetric storage (both halos of N > 1 inside)
         KLE_TRY(c->tic("spmv", &ev));
@@ -989,6 +995,7 @@ int kle_mat_create_aij_csr(kle_ctx *ctx, int64_t m, int64_t n, const int64_t *in
 int kle_mat_set_values(kle_mat *A, int32_t nr, const int64_t *rows, int32_t nc, const int64_t *cols,
                        const double *v, int addv)
 {
+    KLE_NO_ELEM(A, "setValues");
     if (A) sym_drop(A);
     KLE_ARG(A && rows && cols && v, "null arg");
     if (A->kind != 1) return fail(KLE_ERR_SUP, "setValues on a node-block matrix: assemble with kle_assemble_kle");
@@ -1024,6 +1031,7 @@ int kle_mat_set_values(kle_mat *A, int32_t nr, const int64_t *rows, int32_t nc, 
 
 int kle_mat_assemble(kle_mat *A)
 {
+    KLE_NO_ELEM(A, "assemble");
     if (A) sym_drop(A);
     KLE_ARG(A, "null mat");
     if (A->kind != 1) return 0;
@@ -1059,6 +1067,7 @@ int kle_mat_assemble(kle_mat *A)
 int kle_mat_destroy(kle_mat *A)
 {
     if (!A) return 0;
+    elem_drop(A);
     hipFree(A->d_rowcnt);
     hipFree(A->d_rowbox);
     hipFree(A->d_vptr);
@@ -1120,6 +1129,10 @@ int kle_mat_get_info(const kle_mat *A, kle_mat_info *info)
 int kle_mat_get_local_nnz(const kle_mat *A, int64_t *nnz)
 {
     KLE_ARG(A && nnz, "null arg");
+    if (A->kind == 2) {  // no stored entries (kle.h: nz_used of an element-wise operator)
+        *nnz = 0;
+        return 0;
+    }
     if (A->kind == 1) {
         *nnz = A->nnz;
         return 0;
@@ -1153,6 +1166,7 @@ int kle_mat_mult_add(kle_mat *A, kle_vec *x, kle_vec *y, kle_vec *z)
 int kle_mat_diagonal_scale(kle_mat *A, const kle_vec *L, const kle_vec *Rv)
 {
     KLE_ARG(A, "null mat");
+    KLE_NO_ELEM(A, "diagonalScale");
     sym_drop(A);  // the symmetric copy no longer describes the values
     kle_ctx *c = A->ctx;
     if (L && L->n_local != A->m_local) return fail(KLE_ERR_SIZ, "left scaling vector size mismatch");
@@ -1191,6 +1205,7 @@ int kle_mat_get_diagonal(const kle_mat *A, kle_vec *d)
 {
     KLE_ARG(A && d, "null arg");
     KLE_ARG(d->n_local == A->m_local, "diagonal vector size mismatch");
+    if (A->kind == 2) return elem_diagonal(A, d);
     kle_ctx *c = A->ctx;
     if (A->kind == 0) {
         KLE_ARG(A->R == A->C, "get_diagonal needs square blocks");
@@ -1215,6 +1230,7 @@ int kle_mat_get_diagonal(const kle_mat *A, kle_vec *d)
 int kle_mat_get_csr_size(const kle_mat *A, int64_t *m_local, int64_t *nnz)
 {
     KLE_ARG(A && m_local && nnz, "null arg");
+    KLE_NO_ELEM(A, "CSR export");
     *m_local = A->m_local;
     if (A->kind == 1) {
         *nnz = A->assembled ? A->nnz : 0;
@@ -1246,6 +1262,7 @@ int kle_mat_get_csr_size(const kle_mat *A, int64_t *m_local, int64_t *nnz)
 int kle_mat_get_row(const kle_mat *A, int64_t row, int64_t *ncols, int64_t *cols, double *vals)
 {
     KLE_ARG(A && ncols, "null arg");
+    KLE_NO_ELEM(A, "getRow");
     KLE_ARG(row >= A->row_lo && row < A->row_lo + A->m_local, "row %lld not owned", (long long)row);
     const int64_t lr = row - A->row_lo;
     std::vector<int64_t> c;
@@ -1296,6 +1313,7 @@ int kle_mat_get_row(const kle_mat *A, int64_t row, int64_t *ncols, int64_t *cols
 int kle_mat_get_csr(const kle_mat *A, int64_t *indptr, int64_t *indices, double *data)
 {
     KLE_ARG(A && indptr && indices && data, "null arg");
+    KLE_NO_ELEM(A, "CSR export");
     if (A->kind == 1) {
         KLE_HIP(hipMemcpy(data, A->d_aval, sizeof(double) * A->nnz, hipMemcpyDeviceToHost));
         memcpy(indptr, A->h_ptr.data(), sizeof(int64_t) * (A->m_local + 1));
@@ -1333,6 +1351,7 @@ int kle_mat_get_csr(const kle_mat *A, int64_t *indptr, int64_t *indices, double 
 int kle_mat_convert_aij(const kle_mat *A, kle_mat **out)
 {
     KLE_ARG(A && out, "null arg");
+    KLE_NO_ELEM(A, "convert");
     KLE_ARG(A->ctx->nranks == 1, "convert_aij is single-rank");
     int64_t m, z;
     KLE_TRY(kle_mat_get_csr_size(A, &m, &z));
@@ -1354,6 +1373,8 @@ int kle_mat_convert_aij(const kle_mat *A, kle_mat **out)
 int kle_mat_axpy(kle_mat *Y, double a, const kle_mat *X)
 {
     KLE_ARG(Y && X, "null arg");
+    KLE_NO_ELEM(Y, "axpy");
+    KLE_NO_ELEM(X, "axpy");
     sym_drop(Y);
     KLE_ARG(Y->kind == X->kind && Y->m_local == X->m_local && Y->n_local == X->n_local, "layout mismatch");
     kle_ctx *c = Y->ctx;
@@ -1393,6 +1414,7 @@ int kle_mat_axpy(kle_mat *Y, double a, const kle_mat *X)
 int kle_mat_duplicate(const kle_mat *A, int copy_values, kle_mat **out)
 {
     KLE_ARG(A && out, "null arg");
+    KLE_NO_ELEM(A, "duplicate");
     kle_mat *B = new kle_mat(*A);
     B->d_rowcnt = nullptr;
     B->d_rowbox = nullptr;
@@ -1472,6 +1494,7 @@ int kle_mat_set_spmv_structured(kle_mat *A, int on)
 int kle_mat_move_values(kle_mat *A, long long shift, int fresh)
 {
     using namespace kle;
+    KLE_NO_ELEM(A, "moveValues");
     KLE_ARG(A && A->d_sval, "no symmetric storage");
     KLE_ARG(shift >= 0 && shift % 8 == 0 && shift <= (1ll << 30), "shift: a multiple of 8 bytes in [0, 1 GiB]");
     const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(A->snvals, 1);
@@ -1525,6 +1548,7 @@ int kle_mat_get_sym_bricks(const kle_mat *A, int *nbricks, int *dims, double *en
 int kle_mat_set_symmetric(kle_mat *A, int on)
 {
     KLE_ARG(A, "null matrix");
+    KLE_NO_ELEM(A, "symmetric storage");
     if (!on) {
         sym_drop(A);
         return 0;
@@ -1564,7 +1588,7 @@ int kle_set_nb_pad(int quantum)
 int kle_mat_get_format(const kle_mat *A, char *buf, int buflen)
 {
     KLE_ARG(A && buf && buflen > 3, "bad arg");
-    snprintf(buf, buflen, "%s", A->kind == 0 ? "nb" : "aij");
+    snprintf(buf, buflen, "%s", A->kind == 0 ? "nb" : A->kind == 2 ? "elem" : "aij");
     return 0;
 }
 
@@ -1572,7 +1596,9 @@ int kle_mat_spmv_kernel(const kle_mat *A, char *buf, int buflen)
 {
     KLE_ARG(A && buf && buflen > 0, "bad arg");
     std::string s;
-    if (A->kind != 0) {
+    if (A->kind == 2) {
+        s = elem_kernel_name(A);
+    } else if (A->kind != 0) {
         s = "k_aij_spmv<8,4>";
     } else if (A->d_sval && g_tune.spmv_sym) {
         s = sym_kernel_name(A);
@@ -1594,7 +1620,9 @@ int kle_mat_spmv_kernel(const kle_mat *A, char *buf, int buflen)
 int kle_mat_spmv_bytes(const kle_mat *A, double *bytes)
 {
     KLE_ARG(A && bytes, "null arg");
-    if (A->kind == 0 && A->d_sval && g_tune.spmv_sym) {
+    if (A->kind == 2) {
+        *bytes = elem_spmv_bytes(A);
+    } else if (A->kind == 0 && A->d_sval && g_tune.spmv_sym) {
         *bytes = sym_spmv_bytes(A);
     } else if (A->kind == 0) {
         // bytes the SpMV must move: real blocks only (row padding is not counted);
@@ -1617,6 +1645,7 @@ int kle_mat_spmv_bytes(const kle_mat *A, double *bytes)
 int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, double *ms)
 {
     KLE_ARG(A && x && y && ms && reps >= 1, "bad arg");
+    KLE_NO_ELEM(A, "local product timing");
     KLE_TRY(check_mult_layout(A, x, y));
     KLE_ARG(spmv_can_split(A), "local product timing: box-brick symmetric storage only");
     kle_ctx *c = A->ctx;

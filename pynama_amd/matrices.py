@@ -61,6 +61,19 @@ class MatFS:
         A.setName(name)
         return A
 
+    def getElementK(self):
+        """K as an element-wise operator (Mat.createKLEElement): no assembled
+        values, uniform box meshes on one rank.  Created on first use."""
+        if getattr(self, "_elemK", None) is None:
+            self._elemK = Mat.createKLEElement(self.dom.getMesh(), "K")
+        return self._elemK
+
+    def getElementKrhs(self):
+        """Krhs as an element-wise operator; created on first use."""
+        if getattr(self, "_elemKrhs", None) is None:
+            self._elemKrhs = Mat.createKLEElement(self.dom.getMesh(), "Krhs")
+        return self._elemKrhs
+
     def buildOperators(self):
         """Curl / SrT / DivSrT on the device (mat_fs.py:194-201)."""
         self.operator = Operators()

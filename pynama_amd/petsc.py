@@ -337,6 +337,22 @@ class Mat:
         self._keep = d
         return self
 
+    @classmethod
+    def createKLEElement(cls, mesh, which="K"):
+        """Element-wise K or Krhs of a uniform box mesh (kle_mat_create_kle_element):
+        the product is formed from the mesh's one element matrix, no assembled
+        values.  mult, *, createVecLeft/Right, getDiagonal, the size getters,
+        getInfo and spmvKernel work; calls that need stored values raise
+        Error 56, as do unstructured, no-slip and multi-rank meshes."""
+        if which not in ("K", "Krhs"):
+            raise Error(62, f"createKLEElement: which must be 'K' or 'Krhs', not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_kle_element", ctx.h, mesh._h, 0 if which == "K" else 1, C.byref(h))
+        m = cls._wrap(h, ctx, mesh, mesh.dim, mesh.dim)
+        m.setName("element " + which)
+        return m
+
     def setUp(self):
         return self
 
@@ -419,7 +435,8 @@ class Mat:
         try:
             call("kle_mat_set_symmetric", self._h, 1)
         except Error as e:
-            if e.ierr != 56:
+            # (an element-wise operator refuses: it has no values to store)
+            if e.ierr != 56 or self.getFormat() == "elem":
                 raise
 
     def isSymmetric(self, tol=0.0):
@@ -766,6 +783,10 @@ class KSP:
         self._ensure()
         self._A = A
         call("kle_ksp_set_operators", self._h, A._h)
+
+    def getOperators(self):
+        """(A, P) as petsc4py returns them; the preconditioner is built from A."""
+        return self._A, self._A
 
     def setUp(self):
         self._ensure()

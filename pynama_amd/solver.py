@@ -12,6 +12,7 @@ sequential systems up to 40k unknowns (config 1, the unit cases); beyond that,
 or on several ranks, it raises like PETSc without a parallel direct solver --
 there is no CPU fallback.
 """
+from ._lib import Error
 from .petsc import KSP, PC, Options
 
 DEFAULT_RTOL = 1e-10
@@ -34,14 +35,22 @@ class KleSolver:
     def __init__(self):
         self.mat = None
         self._b = None
+        self._Krhs = None  # the element-wise Krhs with -kle_k_type element
 
     def setMat(self, mat):
         self.mat = mat
 
     def setUp(self):
         K = self.mat.K
+        # -kle_k_type element: the KSP's operator and rhs()'s Krhs are the
+        # element-wise operators (MatFS.getElementK / getElementKrhs); whatever
+        # they refuse (unstructured, no-slip, several ranks) raises -- no fallback
+        ktype = Options().getString("kle_k_type", "assembled")
+        if ktype not in ("assembled", "element"):
+            raise Error(62, f"-kle_k_type {ktype}: assembled | element")
+        self._Krhs = self.mat.getElementKrhs() if ktype == "element" else None
         self.solver = KspSolver()
-        self.solver.createSolver(K)
+        self.solver.createSolver(self.mat.getElementK() if ktype == "element" else K)
         self.__vel = K.createVecRight()
         self.__vel.setName("velocity")
         self._b = K.createVecLeft()
@@ -64,7 +73,7 @@ class KleSolver:
         """b = Rw * vort + Krhs * vel (kle_solver.py:35) without temporaries."""
         vel = self.__vel if vec is None else vec
         self.mat.Rw.mult(vort, self._b)
-        self.mat.Krhs.mult(vel, self._wtmp)
+        (self._Krhs or self.mat.Krhs).mult(vel, self._wtmp)
         self._b.axpy(1.0, self._wtmp)
         return self._b
 

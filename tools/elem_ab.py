@@ -1,0 +1,259 @@
+"""In-process A/B of the element-wise K (Mat.createKLEElement, kle_elem.hip)
+against the assembled K as bench.py configures it (symmetric storage, bricks),
+on one GPU: per mesh, legs alternate round by round in ONE process --
+
+  product   --reps products y = K x            (assembled, element)
+  cg        --its fixed iterations of classic Jacobi-CG on each
+
+each timed with HIP events recorded on the context's stream after a warm-up
+of the same leg; the median over --rounds and the rounds' spread are reported.
+The device memory each operator holds is hipMemGetInfo before / after its
+creation.  With --check (first mesh): the product bound of
+tests/test_gpu_elem.py on a 4096-row sample covering every Dirichlet / free
+boundary class (reference rows from the assembled K, np.longdouble; delta
+from the 27 first / middle / last elements per axis), and one converged
+classic-CG solve with the element operator whose true residual is formed
+through the assembled K.  One JSON line per leg is appended to --out.
+
+  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+class Hip:
+    """The few HIP runtime calls the timing needs."""
+
+    def __init__(self, ctx):
+        from pynama_amd._lib import call
+        self.rt = C.CDLL("libamdhip64.so")
+        s = C.c_void_p()
+        call("kle_ctx_get_stream", ctx.h, C.byref(s))
+        self.stream = s
+
+    def _ok(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed: hipError {rc}")
+
+    def free_bytes(self):
+        f, t = C.c_size_t(), C.c_size_t()
+        self._ok(self.rt.hipMemGetInfo(C.byref(f), C.byref(t)), "hipMemGetInfo")
+        return f.value
+
+    def timed_ms(self, fn):
+        e0, e1 = C.c_void_p(), C.c_void_p()
+        self._ok(self.rt.hipEventCreate(C.byref(e0)), "hipEventCreate")
+        self._ok(self.rt.hipEventCreate(C.byref(e1)), "hipEventCreate")
+        try:
+            self._ok(self.rt.hipEventRecord(e0, self.stream), "hipEventRecord")
+            fn()
+            self._ok(self.rt.hipEventRecord(e1, self.stream), "hipEventRecord")
+            self._ok(self.rt.hipEventSynchronize(e1), "hipEventSynchronize")
+            ms = C.c_float()
+            self._ok(self.rt.hipEventElapsedTime(C.byref(ms), e0, e1), "hipEventElapsedTime")
+            return float(ms.value)
+        finally:
+            self.rt.hipEventDestroy(e0)
+            self.rt.hipEventDestroy(e1)
+
+
+def spread(v):
+    m = statistics.median(v)
+    return {"median": m, "min": min(v), "max": max(v), "spread_pct": 100.0 * (max(v) - min(v)) / m}
+
+
+def check_product(pa, np, dom, mat, Ke, nrows=4096):
+    """tests/test_gpu_elem.py's bound on a sample of rows of the full-size mesh."""
+    from pynama_amd._lib import call
+    mesh, dim, ngl = dom.mesh, dom.mesh.dim, dom.mesh.ngl
+    nn, nd, E = ngl ** dim, dim * ngl ** dim, mesh.E
+    ctx = pa.get_ctx()
+    eps = np.finfo(np.float64).eps
+    isdir = np.zeros(mesh.N, bool)
+    isdir[mesh.face_nodes(pa.mesh.FACES[dim])] = True
+    conn = mesh.conn()
+    ninc = np.bincount(conn.ravel(), minlength=mesh.N)
+    # classes: (Dirichlet?, incident elements); the same share of the sample each
+    rng = np.random.default_rng(7)
+    cls = isdir.astype(np.int64) * 16 + ninc
+    keys = np.unique(cls)
+    per = max(1, (nrows // dim) // len(keys) + 1)
+    nodes = np.concatenate([rng.permutation(np.flatnonzero(cls == k))[:per] for k in keys])
+    rows = (nodes[:, None] * dim + np.arange(dim)[None, :]).ravel()[:nrows]
+    # K_e0, Kmax, delta over the first / middle / last elements of every axis
+    K0, Rwe = np.zeros((nd, nd)), np.zeros((nd, (1 if dim == 2 else 3) * nn))
+    call("kle_element_kle", ctx.h, mesh._h, 0, K0, Rwe)
+    Kmax = np.abs(K0).max()
+    ne = list(mesh.nelem) + [1] * (3 - dim)
+    pos = [sorted({0, n // 2, n - 1}) for n in ne]
+    Kx, delta = np.zeros((nd, nd)), 0.0
+    for ez in pos[2]:
+        for ey in pos[1]:
+            for ex in pos[0]:
+                e = ex + ne[0] * (ey + ne[1] * ez)
+                if e:
+                    call("kle_element_kle", ctx.h, mesh._h, e, Kx, Rwe)
+                    delta = max(delta, np.abs(Kx - K0).max() / Kmax)
+    x = np.random.default_rng(20240607).uniform(-1, 1, mesh.N * dim)
+    xv = Ke.createVecRight()
+    xv.setArray(x)
+    y = (Ke * xv).getArray()
+    # node -> incident (element, local node), from the connectivity
+    order = np.argsort(conn.ravel(), kind="stable")
+    start = np.concatenate([[0], np.cumsum(ninc)])
+    dird = np.repeat(isdir, dim)
+    aK0 = np.abs(K0)
+    worst, bad = 0.0, 0
+    for r in rows:
+        cols, vals = mat.K.getRow(int(r))
+        ref = np.sum(vals.astype(np.longdouble) * x[cols].astype(np.longdouble))
+        node, a = divmod(int(r), dim)
+        B = X = 0.0
+        for t in order[start[node]:start[node + 1]]:
+            e, l = divmod(int(t), nn)
+            gd = (conn[e][:, None] * dim + np.arange(dim)[None, :]).ravel()
+            xe = np.where(dird[gd], 0.0, np.abs(x[gd]))
+            B += aK0[l * dim + a] @ xe
+            X += xe.sum()
+        if dird[r]:
+            B = max(B, abs(x[r]))
+        bnd = (nd + 8) * eps * B + delta * Kmax * X
+        err = float(abs(np.longdouble(y[r]) - ref))
+        worst = max(worst, err / bnd if bnd > 0 else (0.0 if err == 0 else np.inf))
+        bad += err > bnd
+    return {"rows": int(len(rows)), "classes": int(len(keys)), "delta": float(delta), "delta_elements": 27,
+            "max_err_over_bound": float(worst), "rows_over_bound": int(bad)}
+
+
+def check_solve(pa, np, mat, Ke):
+    K = mat.K
+    xt = K.createVecRight()
+    xt.setArray(np.random.default_rng(9).uniform(-1, 1, xt.getLocalSize()))
+    b = K * xt
+    out = {}
+    for label, A in (("element", Ke), ("assembled", K)):
+        ksp = pa.petsc.KSP().create()
+        ksp.setType("cg")
+        pc = pa.petsc.PC().create()
+        pc.setType("jacobi")
+        ksp.setPC(pc)
+        ksp.setCGSingleReduction(False)
+        ksp.setTolerances(rtol=1e-10, atol=0.0, max_it=100000)
+        ksp.setOperators(A)
+        ksp.setUp()
+        u = A.createVecRight()
+        ksp.solve(b, u)
+        r = K * u  # the true residual through the assembled K
+        r.aypx(-1.0, b)
+        out[label] = {"iterations": ksp.getIterationNumber(), "reason": ksp.getConvergedReason(),
+                      "correction_iterations": ksp.getCorrectionIterations(),
+                      "true_rel_residual_assembled_K": r.norm() / b.norm()}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--meshes", nargs="+", default=["20,16,16:5", "8,8,6:7"], help="nelem:ngl")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--its", type=int, default=50)
+    ap.add_argument("--check", action="store_true", help="full-size correctness on the first mesh")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "elem", "elem_ab.jsonl"))
+    a = ap.parse_args()
+    import numpy as np
+
+    import pynama_amd as pa
+    ctx = pa.get_ctx()
+    hip = Hip(ctx)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    fout = open(a.out, "a")
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        fout.write(line + "\n")
+        fout.flush()
+
+    for mi, spec in enumerate(a.meshes):
+        ne_s, ngl = spec.split(":")
+        nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+        dim = len(nelem)
+        cfg = {"domain": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * dim, "upper": [1.0] * dim}},
+               "boundary-conditions": {"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}}}
+        dom = pa.Domain()
+        dom.configure(cfg)
+        dom.setUp()
+        ctx.synchronize()
+        m0 = hip.free_bytes()
+        mat = pa.MatFS()
+        mat.setDomain(dom)
+        mat.build(buildOperators=False)
+        ctx.synchronize()
+        m1 = hip.free_bytes()
+        Ke = mat.getElementK()
+        ctx.synchronize()
+        m2 = hip.free_bytes()
+        ops = {"assembled": mat.K, "element": Ke}
+        nd, E = dim * ngl ** dim, dom.mesh.E
+        base = {"nelem": nelem, "ngl": ngl, "dofs": mat.K.getSize()[0], "rounds": a.rounds}
+        x = mat.K.createVecRight()
+        x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+        y = mat.K.createVecLeft()
+        b = mat.K.createVecLeft()
+        b.setArray(np.random.default_rng(2).uniform(-1, 1, b.getLocalSize()))
+        ksps = {}
+        for label, A in ops.items():
+            ksp = pa.petsc.KSP().create()
+            ksp.setType("cg")
+            pc = pa.petsc.PC().create()
+            pc.setType("jacobi")
+            ksp.setPC(pc)
+            ksp.setCGSingleReduction(False)
+            ksp.setOperators(A)
+            ksp.setUp()
+            ksp.setFixedIterations(a.its)
+            ksps[label] = (ksp, A.createVecRight())
+        t_prod = {k: [] for k in ops}
+        t_cg = {k: [] for k in ops}
+        for _ in range(a.rounds):
+            for label, A in ops.items():
+                for _w in range(20):
+                    A.mult(x, y)
+                ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                t_prod[label].append(1e3 * ms / a.reps)
+            for label, (ksp, u) in ksps.items():
+                u.set(0.0)
+                ksp.solve(b, u)  # warm-up: the same fixed iterations
+                u.set(0.0)
+                ms = hip.timed_ms(lambda: ksp.solve(b, u))
+                if ksp.getConvergedReason() < 0:
+                    raise SystemExit(f"elem_ab: the fixed CG iterations diverged ({label})")
+                t_cg[label].append(1e3 * ms / a.its)
+        mem = {"assembled": {"bytes_K_Krhs_Rw": m0 - m1}, "element": {"bytes_K": m1 - m2}}
+        for label, A in ops.items():
+            flops = 2.0 * nd * nd * E if label == "element" else 2.0 * A.getInfo()["nz_used"]
+            emit(dict(base, leg="product", operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(), flops=flops,
+                      reps=a.reps, us=spread(t_prod[label]), device_memory=mem[label]))
+        for label, (ksp, _u) in ksps.items():
+            emit(dict(base, leg="cg", operator=label, ksp="cg (classic) + jacobi", kernel=ops[label].spmvKernel(),
+                      iterations=a.its, us_per_iteration=spread(t_cg[label])))
+        ratio = {"product": statistics.median(t_prod["assembled"]) / statistics.median(t_prod["element"]),
+                 "cg_iteration": statistics.median(t_cg["assembled"]) / statistics.median(t_cg["element"])}
+        emit(dict(base, leg="ratio", assembled_over_element=ratio,
+                  gate_element_cg_not_slower=bool(ratio["cg_iteration"] >= 1.0) if mi == 0 else None))
+        if a.check and mi == 0:
+            emit(dict(base, leg="check_product", **check_product(pa, np, dom, mat, Ke)))
+            emit(dict(base, leg="check_solve", **check_solve(pa, np, mat, Ke)))
+        del ksps, ops, Ke, mat, dom, x, y, b
+    fout.close()
+
+
+if __name__ == "__main__":
+    main()
