@@ -361,8 +361,14 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
 /* Element-wise operator of a uniform box mesh: y = A x formed from the one
  * element matrix of the mesh, no assembled values.  which: 0 K (free rows x
  * free columns + unit Dirichlet diagonal), 1 Krhs (free rows x Dirichlet
- * columns, negated, + unit Dirichlet diagonal): the same operators
- * kle_assemble_kle assembles (MatFS.buildFS, mat_fs.py:150-190).
+ * columns, negated, + unit Dirichlet diagonal), 2 Rw (free rows x every
+ * vorticity column of their elements, no mask and no negation; Dirichlet rows
+ * hold no entry, y_i = 0 exactly; rows dim N by columns dim_w N, dim_w = 1 in
+ * 2-D and 3 in 3-D, blocks dim x dim_w, from the rectangular Rw_e0 of the same
+ * element kernel launch): the same operators
+ * kle_assemble_kle assembles (MatFS.buildFS, mat_fs.py:150-190).  With all
+ * three, b = Rw w + Krhs u_bc and K u = b need no assembly at all
+ * (MatFS.build(kleType="element"), -kle_mat_type element).
  * kle_mesh_create_box makes every element the same brick, so K u = sum_e
  * S_e^T K_e0 S_e u with K_e0 the first local element's matrix (from the
  * assembly's own element kernel): one FP64 MFMA GEMM K_e0 x [gathered element
@@ -371,6 +377,7 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * of the element matrices over the mesh (coordinate rounding, ~1e-15).
  * Memory: K_e0, the connectivity and incidence tables, one Dirichlet flag per
  * node and E * dim * ngl^dim doubles of element results; nothing of nnz(K).
+ * Each operator owns its tables and workspace; nothing is shared between them.
  * The result is a kle_mat of format 2 ("elem").  It supports kle_mat_mult,
  * kle_mat_mult_add, kle_mat_get_diagonal, the size / local-size / ownership
  * getters, kle_mat_get_info (nz_used = 0: no entry is stored),
@@ -379,10 +386,19 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * paths) or gmres and PC none or jacobi.  Calls that need stored
  * values return KLE_ERR_SUP: set_values, assemble, axpy, diagonal_scale,
  * get_row, get_csr, get_csr_size, convert_aij, duplicate, set_symmetric,
- * move_values, time_local_spmv, PC lu.
+ * move_values, time_local_spmv, PC lu.  Rw also refuses kle_mat_get_diagonal
+ * (KLE_ERR_SUP), and kle_ksp_set_operators refuses a non-square operator
+ * (the 2-D Rw) before anything is launched.
  * Needs a box mesh with its Dirichlet set, 2-D or 3-D, on one rank;
  * KLE_ERR_SUP for unstructured meshes, no-slip meshes and nranks > 1. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* dst_i = src_i on the Dirichlet rows of an element-wise operator (its own
+ * Dirichlet flags; rows dim N), every other entry of dst untouched; on the
+ * context's stream, no synchronisation.  KleSolver uses it after a
+ * matrix-free solve: the unit Dirichlet rows make u_i = b_i = u_bc exactly,
+ * which a Krylov iteration started from 0 reaches only to its tolerance.
+ * KLE_ERR_SUP for any other matrix kind. */
+int kle_mat_copy_dirichlet_rows(const kle_mat *A, const kle_vec *src, kle_vec *dst);
 
 /* Generic AIJ (petsc4py Mat().createAIJ + setValues + assemble). */
 int kle_mat_create_aij(kle_ctx *ctx, int64_t m_local, int64_t n_local, int64_t m_global,

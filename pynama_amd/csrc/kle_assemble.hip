@@ -1298,9 +1298,12 @@ static int element_matrices(kle_ctx *ctx, const kle_mesh *m, double **dKe, doubl
 // K_e of the first local element alone, as blocks [l][m][a][b] in a new device
 // buffer: the geometry and element kernels of the assembly on that element's
 // own corners, so the values are the ones the assembled K received from it
-// (the element-wise operator, kle_elem.hip).
-int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe)
+// (the element-wise operator, kle_elem.hip).  With dRwe_out the Rw_e the same
+// launch forms, blocks [l][m][a][b] with b < dim_w, is handed out as well (the
+// caller frees both); without it, it is freed here.
+int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe, double **dRwe_out)
 {
+    if (dRwe_out) *dRwe_out = nullptr;
     const int dim = m->dim, ne = m->nn(), dw = dim == 2 ? 1 : 3;
     ElemSetup S;
     KLE_TRY(element_setup(ctx, m, S, 1));
@@ -1316,7 +1319,8 @@ int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe)
     }
     int rc = element_batch(ctx, m, S, 0, 1, *dKe, dRwe, nullptr);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(KLE_ERR_DEVICE, "element kernel failed");
-    hipFree(dRwe);
+    if (rc || !dRwe_out) hipFree(dRwe);
+    else *dRwe_out = dRwe;
     if (rc) {
         hipFree(*dKe);
         *dKe = nullptr;

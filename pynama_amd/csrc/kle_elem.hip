@@ -1,4 +1,4 @@
-// kle_elem.hip -- element-wise K and Krhs of a uniform box mesh (kle_mat kind 2).
+// kle_elem.hip -- element-wise K, Krhs and Rw of a uniform box mesh (kle_mat kind 2).
 //
 // kle_mesh_create_box makes every element the same brick, so every element
 // matrix equals that of the first element up to coordinate rounding and
@@ -8,7 +8,10 @@
 // with the Dirichlet masking of MatFS.buildFS (mat_fs.py:150-190): no matrix
 // values are stored or streamed.  K_e0 (nd x nd, nd = dim * ngl^dim) stays in
 // cache; the product is one FP64 GEMM K_e0 [nd x nd] * X [nd x E] followed by
-// a gather per node.
+// a gather per node.  Rw (mat_fs.py:185-186) is the same construction with the
+// rectangular Rw_e0 [nd x nc], nc = dim_w * ngl^dim (dim_w = 1 in 2-D, 3 in
+// 3-D): free rows take every vorticity column of their elements (no column
+// mask, no negation), Dirichlet rows hold no entry.
 //
 //   k_elem_gemm    one 256-thread workgroup per (batch of 16 * NCT elements,
 //                  NCT = 2 or 1; group of 128 rows).  The batch's x entries
@@ -25,11 +28,17 @@
 //                  Loads run a chunk (operands, x) or two (node ids) ahead of
 //                  the MFMAs in registers.  Rows and columns beyond nd and
 //                  elements beyond E are zero operands and are never stored.
+//                  The contraction runs over the nc columns of the element
+//                  matrix, padded to the k step of 4 (ncp); x is gathered as
+//                  x[node * CW + b], CW the component count of the column
+//                  space (dim for K and Krhs, dim_w for Rw), so a padding
+//                  column is a zero operand and is never read from x.
 //                  Krhs negates the result (the assembly adds -K_e).
 //   k_elem_gather  one thread per owned DoF: the sum of its node's incidence
 //                  entries from the element results in table (ascending
 //                  element) order -- fixed order, no atomics, bitwise
-//                  repeatable.  Dirichlet rows: y_i = x_i (both operators).
+//                  repeatable.  Dirichlet rows: y_i = x_i (K, Krhs); 0 for Rw,
+//                  which reads neither x nor the element results there.
 #include <algorithm>
 #include <cstring>
 
@@ -38,10 +47,10 @@
 namespace kle {
 
 struct ElemOp {
-    int which = 0, dim = 3, nn = 0, nd = 0, ndp = 0, maxinc = 8, nct = 1;
+    int which = 0, dim = 3, cw = 3, nn = 0, nd = 0, ndp = 0, nc = 0, ncp = 0, maxinc = 8, nct = 1;
     int64_t E = 0, N = 0;
-    double *d_kt = nullptr;     // K_e0 padded to ndp x ndp in MFMA operand order [row tile][k step][lane]
-    double *d_kdiag = nullptr;  // [nd] its diagonal
+    double *d_kt = nullptr;     // K_e0 (Rw_e0) padded to ndp x ncp in MFMA operand order [row tile][k step][lane]
+    double *d_kdiag = nullptr;  // [nd] its diagonal (K, Krhs)
     double *d_ws = nullptr;     // [E][nd] element results
     int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order; -1 where the operator drops the entry
     int32_t *d_inc = nullptr;   // [N][maxinc] node -> e * nn + l, ascending e, -1 padded
@@ -54,8 +63,8 @@ constexpr int EG_ROWS = 4 * EG_TR * 16;  // rows per workgroup
 
 typedef double edbl4 __attribute__((ext_vector_type(4)));
 
-template <int DIM, int NCT>
-__global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int64_t E,
+template <int CW, int NCT>
+__global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int nc, int ncp, int64_t E,
                                                       const double *__restrict__ kt,
                                                       const int32_t *__restrict__ mconn,
                                                       const double *__restrict__ x, double *__restrict__ ws,
@@ -70,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd
     const int li = lane & 15, kq = lane >> 4;
     const int64_t e0 = (int64_t)blockIdx.x * NE;
     const int rt0 = ((int)blockIdx.y * 4 + wv) * EG_TR;  // this wave's first row tile
-    const int ntile = ndp >> 4, nks = ndp >> 2;
+    const int ntile = ndp >> 4, nks = ncp >> 2;
 
     const edbl4 z4 = {0.0, 0.0, 0.0, 0.0};
     edbl4 acc[EG_TR][NCT];
@@ -82,27 +91,27 @@ __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd
     // Three loads deep: while chunk c runs its MFMAs, the x entries and the
     // K_e0 operands of chunk c + 1 and the node ids of chunk c + 2 are in
     // flight.  Node ids come through the masked connectivity (-1: dropped --
-    // selection, the entry is never read; also beyond nd, E and the last chunk).
+    // selection, the entry is never read; also beyond nc, E and the last chunk).
     int nr[NPT];
     double xr[NPT], ar[EG_TR][KS], an[EG_TR][KS];
     auto fetch_idx = [&](int k0) {
         const int g = k0 + lane;
-        const int l = g / DIM;
+        const int l = g / CW;
 #pragma unroll
         for (int i = 0; i < NPT; ++i) {
             const int64_t e = e0 + wv + 4 * i;
-            nr[i] = g < nd && e < E ? mconn[e * nn + l] : -1;
+            nr[i] = g < nc && e < E ? mconn[e * nn + l] : -1;
         }
     };
     auto fetch_x = [&](int k0) {
         const int g = k0 + lane;
-        const int a = g - (g / DIM) * DIM;
+        const int a = g - (g / CW) * CW;
 #pragma unroll
-        for (int i = 0; i < NPT; ++i) xr[i] = nr[i] >= 0 ? x[(int64_t)nr[i] * DIM + a] : 0.0;
+        for (int i = 0; i < NPT; ++i) xr[i] = nr[i] >= 0 ? x[(int64_t)nr[i] * CW + a] : 0.0;
     };
     // (a tile beyond the last re-reads the wave's first: its sums are never stored)
     auto fetch_a = [&](int k0, double (&t)[EG_TR][KS]) {
-        const int nksc = max(min(EG_KC, ndp - k0), 0) >> 2;
+        const int nksc = max(min(EG_KC, ncp - k0), 0) >> 2;
         if (rt0 >= ntile) return;
 #pragma unroll
         for (int j = 0; j < EG_TR; ++j) {
@@ -115,8 +124,8 @@ __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd
     fetch_a(0, ar);
     fetch_x(0);
     fetch_idx(EG_KC);
-    for (int k0 = 0; k0 < ndp; k0 += EG_KC) {
-        const int nksc = min(EG_KC, ndp - k0) >> 2;
+    for (int k0 = 0; k0 < ncp; k0 += EG_KC) {
+        const int nksc = min(EG_KC, ncp - k0) >> 2;
 #pragma unroll
         for (int i = 0; i < NPT; ++i) sX[lane * SX + wv + 4 * i] = xr[i];
         __syncthreads();
@@ -169,7 +178,9 @@ __global__ __launch_bounds__(256) void k_elem_gather(int64_t N, int nn, int nd, 
     const int64_t node = i / DIM;
     const int a = (int)(i - node * DIM);
     if (dir[node]) {
-        y[i] = x[i];  // setIndices2One: unit Dirichlet diagonal of K and of Krhs
+        // setIndices2One: unit Dirichlet diagonal of K and of Krhs; Rw (x null:
+        // another column space) holds no entry in the row
+        y[i] = x ? x[i] : 0.0;
         return;
     }
     double s = 0.0;
@@ -208,6 +219,15 @@ __global__ __launch_bounds__(256) void k_elem_diag(int64_t N, int nn, int maxinc
     d[i] = s;
 }
 
+// dst_i = src_i on the Dirichlet rows, nothing else touched
+__global__ __launch_bounds__(256) void k_elem_copy_dirichlet(int64_t n, int dim, const uint8_t *__restrict__ dir,
+                                                             const double *__restrict__ src, double *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (dir[i / dim]) dst[i] = src[i];
+}
+
 // Every index the device tables hold, checked on the host before upload: a
 // bad table is an error code, never an out-of-range access.
 static int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E,
@@ -239,12 +259,12 @@ static int elem_validate(const std::vector<int32_t> &conn, const std::vector<int
     return 0;
 }
 
-template <int DIM>
+template <int CW>
 static void launch_gemm(const ElemOp *P, dim3 grid, hipStream_t st, const double *x, const int *istate)
 {
-#define KLE_ELEM_GEMM(NCT)                                                                                   \
-    hipLaunchKernelGGL((k_elem_gemm<DIM, NCT>), grid, dim3(256), 0, st, P->which, P->nn, P->nd, P->ndp, P->E, \
-                       P->d_kt, P->d_conn, x, P->d_ws, istate)
+#define KLE_ELEM_GEMM(NCT)                                                                                      \
+    hipLaunchKernelGGL((k_elem_gemm<CW, NCT>), grid, dim3(256), 0, st, P->which == 1, P->nn, P->nd, P->ndp, P->nc, \
+                       P->ncp, P->E, P->d_kt, P->d_conn, x, P->d_ws, istate)
     if (P->nct == 2) KLE_ELEM_GEMM(2);
     else KLE_ELEM_GEMM(1);
 #undef KLE_ELEM_GEMM
@@ -260,17 +280,19 @@ int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
     hipStream_t st = A->ctx->stream;
     const int ne = 16 * P->nct;
     dim3 grid((unsigned)((P->E + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS));
-    if (P->dim == 2) launch_gemm<2>(P, grid, st, x->d, istate);
+    if (P->cw == 1) launch_gemm<1>(P, grid, st, x->d, istate);
+    else if (P->cw == 2) launch_gemm<2>(P, grid, st, x->d, istate);
     else launch_gemm<3>(P, grid, st, x->d, istate);
     KLE_HIP(hipGetLastError());
     const int64_t n = P->N * P->dim;
     dim3 gg((unsigned)((n + 255) / 256));
+    const double *xd = P->which == 2 ? nullptr : x->d;  // Rw: no Dirichlet diagonal, x is never read by the gather
     if (P->dim == 2)
         hipLaunchKernelGGL(k_elem_gather<2>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->d_inc, P->d_dir,
-                           P->d_ws, x->d, y->d, istate);
+                           P->d_ws, xd, y->d, istate);
     else
         hipLaunchKernelGGL(k_elem_gather<3>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->d_inc, P->d_dir,
-                           P->d_ws, x->d, y->d, istate);
+                           P->d_ws, xd, y->d, istate);
     KLE_HIP(hipGetLastError());
     return 0;
 }
@@ -279,6 +301,7 @@ int elem_diagonal(const kle_mat *A, kle_vec *d)
 {
     const ElemOp *P = A->elem;
     if (!P) return fail(KLE_ERR_STATE, "element operator without tables");
+    if (P->which == 2) return fail(KLE_ERR_SUP, "getDiagonal: the element-wise Rw is rectangular");
     hipStream_t st = A->ctx->stream;
     const int64_t n = P->N * P->dim;
     dim3 gg((unsigned)((n + 255) / 256));
@@ -313,7 +336,7 @@ double elem_spmv_bytes(const kle_mat *A)
 {
     const ElemOp *P = A->elem;
     if (!P) return 0.0;
-    return 8.0 * P->nd * P->nd + 4.0 * P->E * P->nn + 4.0 * P->N * P->maxinc + 1.0 * P->N +
+    return 8.0 * P->nd * P->nc + 4.0 * P->E * P->nn + 4.0 * P->N * P->maxinc + 1.0 * P->N +
            8.0 * A->n_local + 8.0 * A->m_local + 2.0 * 8.0 * P->E * P->nd;
 }
 
@@ -321,27 +344,45 @@ std::string elem_kernel_name(const kle_mat *A)
 {
     const ElemOp *P = A->elem;
     if (!P) return "?";
-    const std::string d = std::to_string(P->dim);
-    return "k_elem_gemm<" + d + "," + std::to_string(P->nct) + ">+k_elem_gather<" + d + ">";
+    return "k_elem_gemm<" + std::to_string(P->cw) + "," + std::to_string(P->nct) + ">+k_elem_gather<" +
+           std::to_string(P->dim) + ">";
 }
 
 }  // namespace kle
 
 using namespace kle;
 
+extern "C" int kle_mat_copy_dirichlet_rows(const kle_mat *A, const kle_vec *src, kle_vec *dst)
+{
+    KLE_ARG(A && src && dst, "null arg");
+    if (A->kind != 2 || !A->elem)
+        return fail(KLE_ERR_SUP, "copyDirichletRows: an element-wise operator only (it holds the Dirichlet flags)");
+    const ElemOp *P = A->elem;
+    const int64_t n = P->N * P->dim;
+    if (src->n_local != n || dst->n_local != n)
+        return fail(KLE_ERR_SIZ, "copyDirichletRows: vectors do not match the operator's rows");
+    if (src->d == dst->d) return 0;
+    hipLaunchKernelGGL(k_elem_copy_dirichlet, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, A->ctx->stream, n, P->dim,
+                       P->d_dir, src->d, dst->d);
+    KLE_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
 {
     KLE_ARG(ctx && m && out, "null arg");
-    KLE_ARG(which == 0 || which == 1, "which must be 0 (K) or 1 (Krhs)");
+    KLE_ARG(which >= 0 && which <= 2, "which must be 0 (K), 1 (Krhs) or 2 (Rw)");
     if (m->kind != 0) return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
     if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "element-wise operator: no-slip meshes are not supported");
     if (m->nranks > 1 || ctx->nranks > 1)
         return fail(KLE_ERR_SUP, "element-wise operator: one rank only (%d ranks)", std::max(m->nranks, ctx->nranks));
     KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+    // rows nd = dim nn (padded to the row tile); columns nc = cw nn (padded to the k step)
     const int dim = m->dim, nn = m->nn(), nd = dim * nn, ndp = (nd + 15) & ~15, maxinc = 1 << dim;
+    const int cw = which == 2 ? (dim == 2 ? 1 : 3) : dim, nc = cw * nn, ncp = (nc + 3) & ~3;
     const int64_t E = m->elem_end - m->elem_begin, N = m->node_end - m->node_begin;
     KLE_ARG(E >= 1 && N >= 1 && m->ext_begin == 0 && m->node_begin == 0 && m->ext_end == N, "unexpected one-rank layout");
-    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
+    if (E * nn >= INT32_MAX || N * std::max(dim, cw) >= INT32_MAX)
         return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
     if ((int64_t)m->dir.size() != N) return fail(KLE_ERR_SIZ, "element operator: Dirichlet flags do not match the mesh");
 
@@ -361,45 +402,52 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     }
     KLE_TRY(elem_validate(conn, inc, N, E, nn, maxinc));
     // the mask rule folded into the connectivity the GEMM reads: K drops the
-    // Dirichlet entries of x, Krhs the free ones
-    for (int64_t k = 0; k < E * nn; ++k)
-        if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
+    // Dirichlet entries of x, Krhs the free ones, Rw none
+    if (which != 2)
+        for (int64_t k = 0; k < E * nn; ++k)
+            if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
 
     KLE_HIP(hipSetDevice(ctx->device));
-    // K_e0 through the assembly's own geometry and element kernels
-    double *dKe = nullptr;
-    KLE_TRY(element_first_k(ctx, m, &dKe));
-    std::vector<double> kb((size_t)nd * nd);
-    hipError_t he = hipMemcpy(kb.data(), dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
+    // K_e0 (Rw_e0) through the assembly's own geometry and element kernels
+    double *dKe = nullptr, *dRwe = nullptr;
+    KLE_TRY(element_first_k(ctx, m, &dKe, which == 2 ? &dRwe : nullptr));
+    std::vector<double> kb((size_t)nd * nc);
+    hipError_t he = hipMemcpy(kb.data(), which == 2 ? dRwe : dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
     (void)hipFree(dKe);
+    (void)hipFree(dRwe);
     if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element matrix download failed: %s", hipGetErrorString(he));
-    // blocks [l][m][a][b] -> K[l dim + a][m dim + b], zero-padded to ndp, in operand order
+    // blocks [l][m][a][b], b < cw -> K[l dim + a][m cw + b], zero-padded to ndp x ncp, in operand order
     auto kat = [&](int r, int c) {
-        return kb[(((size_t)(r / dim) * nn + c / dim) * dim + r % dim) * dim + c % dim];
+        return kb[(((size_t)(r / dim) * nn + c / cw) * dim + r % dim) * cw + c % cw];
     };
-    std::vector<double> kt((size_t)ndp * ndp, 0.0), kdiag((size_t)nd);
-    const int nks = ndp / 4;
+    std::vector<double> kt((size_t)ndp * ncp, 0.0), kdiag((size_t)(which == 2 ? 0 : nd));
+    const int nks = ncp / 4;
     for (int rt = 0; rt < ndp / 16; ++rt)
         for (int ks = 0; ks < nks; ++ks)
             for (int lane = 0; lane < 64; ++lane) {
                 const int r = rt * 16 + (lane & 15), c = ks * 4 + (lane >> 4);
-                if (r < nd && c < nd) kt[((size_t)rt * nks + ks) * 64 + lane] = kat(r, c);
+                if (r < nd && c < nc) kt[((size_t)rt * nks + ks) * 64 + lane] = kat(r, c);
             }
-    for (int r = 0; r < nd; ++r) kdiag[r] = kat(r, r);
+    for (size_t r = 0; r < kdiag.size(); ++r) kdiag[r] = kat((int)r, (int)r);
 
     kle_mat *A = new kle_mat;
     ElemOp *P = new ElemOp;
     A->ctx = ctx;
     A->kind = 2;
     A->elem = P;
-    A->R = A->C = dim;
+    A->R = dim;
+    A->C = cw;
     A->nrows = N;
-    A->m_global = A->n_global = A->m_local = A->n_local = N * dim;
+    A->m_global = A->m_local = N * dim;
+    A->n_global = A->n_local = N * cw;
     P->which = which;
     P->dim = dim;
+    P->cw = cw;
     P->nn = nn;
     P->nd = nd;
     P->ndp = ndp;
+    P->nc = nc;
+    P->ncp = ncp;
     P->maxinc = maxinc;
     P->E = E;
     P->N = N;
@@ -417,7 +465,7 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
         return src ? h2d(*dp, src, bytes) : 0;
     };
     int rc = up(&P->d_kt, kt.data(), sizeof(double) * kt.size());
-    if (!rc) rc = up(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
+    if (!rc && !kdiag.empty()) rc = up(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
     if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);

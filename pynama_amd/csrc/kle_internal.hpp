@@ -404,7 +404,7 @@ int halo_reverse(kle_ctx *ctx, const double *send_hi, int64_t n_send, int hi_ran
 int halo_reverse_plan(kle_ctx *ctx, const HaloPlan &P, int64_t hi0, int bs, const double *gsend, double *rbuf,
                       hipStream_t st);  // kle_core.hip
 // element-wise operator (kle_elem.hip; kle_mat kind 2)
-int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe);  // kle_assemble.hip
+int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe, double **dRwe_out = nullptr);  // kle_assemble.hip
 int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
 int elem_diagonal(const kle_mat *A, kle_vec *d);
 void elem_drop(kle_mat *A);

@@ -12,8 +12,18 @@ import ctypes as C
 import numpy as np
 
 from ._lib import Error, call
-from .petsc import Mat
+from .petsc import Mat, Options
 from .runtime import get_ctx
+
+
+def kle_mat_type(kleType=None):
+    """The form of the KLE matrices: the keyword, else -kle_mat_type, else
+    "assembled"; anything but assembled | element raises Error 62."""
+    if kleType is None:
+        kleType = Options().getString("kle_mat_type", "assembled")
+    if kleType not in ("assembled", "element"):
+        raise Error(62, f"-kle_mat_type {kleType}: assembled | element")
+    return kleType
 
 
 class MatFS:
@@ -27,17 +37,31 @@ class MatFS:
     def setDomain(self, dom):
         self.dom = dom
 
-    def build(self, buildKLE=True, buildOperators=True):
+    def build(self, buildKLE=True, buildOperators=True, kleType=None):
+        """kleType (default: -kle_mat_type, default "assembled"): "element"
+        builds K, Krhs and Rw as element-wise operators and assembles nothing
+        (uniform box meshes on one rank; anything else raises Error 56)."""
         if self.dom.getBoundaryType() != "FS":
             raise Error(56, "MatFS needs free-slip (Dirichlet) boundaries")
         if buildKLE:
-            self.buildFS()
+            self.buildFS(kle_mat_type(kleType))
         if buildOperators:
             self.buildOperators()
 
-    def buildFS(self):
+    def buildFS(self, kleType="assembled"):
         ctx = get_ctx()
         mesh = self.dom.getMesh()
+        dim = self.dom.getDimensions()[0]
+        if kleType == "element":
+            # matrix-free: no kle_assemble_kle, no assembled values; the three
+            # operators are the ones getElementK/Krhs/Rw return
+            self.K, self.Krhs, self.Rw = (Mat.createKLEElement(mesh, n) for n in ("K", "Krhs", "Rw"))
+            for m, n in ((self.K, "K"), (self.Krhs, "Krhs"), (self.Rw, "Rw")):
+                m.setName(n)
+            self._elemK, self._elemKrhs, self._elemRw = self.K, self.Krhs, self.Rw
+            self.Rd = self._empty(dim)
+            self.kle = [self.K, self.Krhs, self.Rw, self.Rd]
+            return
         hK, hKr, hRw = C.c_void_p(), C.c_void_p(), C.c_void_p()
         call("kle_assemble_kle", ctx.h, mesh._h, C.byref(hK), C.byref(hKr), C.byref(hRw))
         dim, dim_w, _ = self.dom.getDimensions()
@@ -74,8 +98,15 @@ class MatFS:
             self._elemKrhs = Mat.createKLEElement(self.dom.getMesh(), "Krhs")
         return self._elemKrhs
 
+    def getElementRw(self):
+        """Rw as an element-wise operator; created on first use."""
+        if getattr(self, "_elemRw", None) is None:
+            self._elemRw = Mat.createKLEElement(self.dom.getMesh(), "Rw")
+        return self._elemRw
+
     def buildOperators(self):
-        """Curl / SrT / DivSrT on the device (mat_fs.py:194-201)."""
+        """Curl / SrT / DivSrT on the device (mat_fs.py:194-201): assembled,
+        whatever the kleType."""
         self.operator = Operators()
         self.operator.setDimensions(self.dom.getDimensions())
         self.operator.build(self.dom.getMesh())
@@ -100,7 +131,9 @@ class MatNS(MatFS):
         self.Kfs = self.Krhsfs = self.Rwfs = self.Rdfs = None
         self._Ksum = None
 
-    def build(self, buildKLE=True, buildOperators=True):
+    def build(self, buildKLE=True, buildOperators=True, kleType=None):
+        if kle_mat_type(kleType) == "element":
+            raise Error(56, "-kle_mat_type element: no-slip matrices have no element-wise form")
         if self.dom.getBoundaryType() != "NS":
             raise Error(56, "MatNS needs no-slip boundaries")
         if buildKLE:

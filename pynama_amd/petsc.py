@@ -339,19 +339,27 @@ class Mat:
 
     @classmethod
     def createKLEElement(cls, mesh, which="K"):
-        """Element-wise K or Krhs of a uniform box mesh (kle_mat_create_kle_element):
+        """Element-wise K, Krhs or Rw of a uniform box mesh (kle_mat_create_kle_element):
         the product is formed from the mesh's one element matrix, no assembled
-        values.  mult, *, createVecLeft/Right, getDiagonal, the size getters,
+        values.  Rw is [dim N x dim_w N] (dim_w = 1 in 2-D, 3 in 3-D).  mult, *,
+        multAdd, createVecLeft/Right, getDiagonal (K, Krhs), the size getters,
         getInfo and spmvKernel work; calls that need stored values raise
         Error 56, as do unstructured, no-slip and multi-rank meshes."""
-        if which not in ("K", "Krhs"):
-            raise Error(62, f"createKLEElement: which must be 'K' or 'Krhs', not {which!r}")
+        kinds = {"K": 0, "Krhs": 1, "Rw": 2}
+        if which not in kinds:
+            raise Error(62, f"createKLEElement: which must be 'K', 'Krhs' or 'Rw', not {which!r}")
         ctx = get_ctx()
         h = C.c_void_p()
-        call("kle_mat_create_kle_element", ctx.h, mesh._h, 0 if which == "K" else 1, C.byref(h))
-        m = cls._wrap(h, ctx, mesh, mesh.dim, mesh.dim)
+        call("kle_mat_create_kle_element", ctx.h, mesh._h, kinds[which], C.byref(h))
+        dim_w = 1 if mesh.dim == 2 else 3
+        m = cls._wrap(h, ctx, mesh, mesh.dim, dim_w if which == "Rw" else mesh.dim)
         m.setName("element " + which)
         return m
+
+    def copyDirichletRows(self, src, dst):
+        """dst[i] = src[i] on the Dirichlet rows of an element-wise operator,
+        nothing else touched (kle_mat_copy_dirichlet_rows)."""
+        call("kle_mat_copy_dirichlet_rows", self._h, src._h, dst._h)
 
     def setUp(self):
         return self

@@ -35,20 +35,26 @@ class KleSolver:
     def __init__(self):
         self.mat = None
         self._b = None
-        self._Krhs = None  # the element-wise Krhs with -kle_k_type element
+        self._Krhs = self._Rw = None  # the element-wise Krhs and Rw with -kle_k_type element
+        self._exactBC = False
 
     def setMat(self, mat):
         self.mat = mat
 
     def setUp(self):
         K = self.mat.K
-        # -kle_k_type element: the KSP's operator and rhs()'s Krhs are the
-        # element-wise operators (MatFS.getElementK / getElementKrhs); whatever
-        # they refuse (unstructured, no-slip, several ranks) raises -- no fallback
+        # -kle_k_type element: the KSP's operator and rhs()'s Krhs and Rw are the
+        # element-wise operators (MatFS.getElementK / getElementKrhs /
+        # getElementRw); whatever they refuse (unstructured, no-slip, several
+        # ranks) raises -- no fallback.  After a matrix-free build
+        # (-kle_mat_type element) mat.K, mat.Krhs and mat.Rw are those already.
         ktype = Options().getString("kle_k_type", "assembled")
         if ktype not in ("assembled", "element"):
             raise Error(62, f"-kle_k_type {ktype}: assembled | element")
         self._Krhs = self.mat.getElementKrhs() if ktype == "element" else None
+        self._Rw = self.mat.getElementRw() if ktype == "element" else None
+        # matrix-free build: solve() hands back the Dirichlet values exactly
+        self._exactBC = K.getFormat() == "elem"
         self.solver = KspSolver()
         self.solver.createSolver(self.mat.getElementK() if ktype == "element" else K)
         self.__vel = K.createVecRight()
@@ -72,7 +78,7 @@ class KleSolver:
     def rhs(self, vort, vec=None):
         """b = Rw * vort + Krhs * vel (kle_solver.py:35) without temporaries."""
         vel = self.__vel if vec is None else vec
-        self.mat.Rw.mult(vort, self._b)
+        (self._Rw or self.mat.Rw).mult(vort, self._b)
         (self._Krhs or self.mat.Krhs).mult(vel, self._wtmp)
         self._b.axpy(1.0, self._wtmp)
         return self._b
@@ -81,6 +87,11 @@ class KleSolver:
         vel = self.__vel if vec is None else vec
         b = self.rhs(vort, vel)
         self.solver(b, vel)
+        if self._exactBC:
+            # the Dirichlet rows of K are unit rows, so there u = b = u_bc; the
+            # Krylov iterate (started from 0) holds them to rtol only.  _wtmp is
+            # Krhs * vel from rhs(): the Dirichlet values as they came in.
+            self.mat.K.copyDirichletRows(self._wtmp, vel)
 
     def getSolution(self):
         return self.__vel

@@ -15,14 +15,31 @@ from the 27 first / middle / last elements per axis), and one converged
 classic-CG solve with the element operator whose true residual is formed
 through the assembled K.  One JSON line per leg is appended to --out.
 
-  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
+With --matfree the legs are those of the matrix-free KLE system instead
+(records to profiles/elem/matfree.jsonl), per mesh and in one process:
+
+  build       wall time of MatFS.build(buildOperators=False) and the device
+              memory its K, Krhs, Rw (and the empty Rd) hold (hipMemGetInfo
+              before / after), kleType assembled and element alternating,
+              after one untimed build of each
+  product_Rw  --reps products y = Rw w      (assembled, element), timed as above
+
+and with --check (first mesh) the Rw product bound of
+tests/test_gpu_matfree.py on the row sample (reference rows from the
+assembled Rw) and one KleSolver.solve on Taylor-Green from the matrix-free
+build, its true residual K u - (Rw w + Krhs u_bc) formed through the assembled
+matrices.
+
+  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check] [--matfree]
 """
 import argparse
 import ctypes as C
+import gc
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -69,11 +86,15 @@ def spread(v):
     return {"median": m, "min": min(v), "max": max(v), "spread_pct": 100.0 * (max(v) - min(v)) / m}
 
 
-def check_product(pa, np, dom, mat, Ke, nrows=4096):
-    """tests/test_gpu_elem.py's bound on a sample of rows of the full-size mesh."""
+def check_product(pa, np, dom, mat, Ke, nrows=4096, which="K"):
+    """tests/test_gpu_elem.py's bound (which "Rw": tests/test_gpu_matfree.py's,
+    Ke the element-wise Rw, reference rows from mat.Rw) on a sample of rows of
+    the full-size mesh."""
     from pynama_amd._lib import call
     mesh, dim, ngl = dom.mesh, dom.mesh.dim, dom.mesh.ngl
     nn, nd, E = ngl ** dim, dim * ngl ** dim, mesh.E
+    rw = which == "Rw"
+    cw = (1 if dim == 2 else 3) if rw else dim  # components of the column space
     ctx = pa.get_ctx()
     eps = np.finfo(np.float64).eps
     isdir = np.zeros(mesh.N, bool)
@@ -87,9 +108,11 @@ def check_product(pa, np, dom, mat, Ke, nrows=4096):
     per = max(1, (nrows // dim) // len(keys) + 1)
     nodes = np.concatenate([rng.permutation(np.flatnonzero(cls == k))[:per] for k in keys])
     rows = (nodes[:, None] * dim + np.arange(dim)[None, :]).ravel()[:nrows]
-    # K_e0, Kmax, delta over the first / middle / last elements of every axis
+    # K_e0 (Rw_e0), Kmax, delta over the first / middle / last elements of every axis
     K0, Rwe = np.zeros((nd, nd)), np.zeros((nd, (1 if dim == 2 else 3) * nn))
     call("kle_element_kle", ctx.h, mesh._h, 0, K0, Rwe)
+    if rw:
+        K0 = Rwe.copy()
     Kmax = np.abs(K0).max()
     ne = list(mesh.nelem) + [1] * (3 - dim)
     pos = [sorted({0, n // 2, n - 1}) for n in ne]
@@ -100,8 +123,8 @@ def check_product(pa, np, dom, mat, Ke, nrows=4096):
                 e = ex + ne[0] * (ey + ne[1] * ez)
                 if e:
                     call("kle_element_kle", ctx.h, mesh._h, e, Kx, Rwe)
-                    delta = max(delta, np.abs(Kx - K0).max() / Kmax)
-    x = np.random.default_rng(20240607).uniform(-1, 1, mesh.N * dim)
+                    delta = max(delta, np.abs((Rwe if rw else Kx) - K0).max() / Kmax)
+    x = np.random.default_rng(20240607).uniform(-1, 1, mesh.N * cw)
     xv = Ke.createVecRight()
     xv.setArray(x)
     y = (Ke * xv).getArray()
@@ -110,26 +133,33 @@ def check_product(pa, np, dom, mat, Ke, nrows=4096):
     start = np.concatenate([[0], np.cumsum(ninc)])
     dird = np.repeat(isdir, dim)
     aK0 = np.abs(K0)
-    worst, bad = 0.0, 0
+    worst, bad, dir_nonzero = 0.0, 0, 0
     for r in rows:
-        cols, vals = mat.K.getRow(int(r))
+        cols, vals = (mat.Rw if rw else mat.K).getRow(int(r))
         ref = np.sum(vals.astype(np.longdouble) * x[cols].astype(np.longdouble))
         node, a = divmod(int(r), dim)
         B = X = 0.0
         for t in order[start[node]:start[node + 1]]:
             e, l = divmod(int(t), nn)
-            gd = (conn[e][:, None] * dim + np.arange(dim)[None, :]).ravel()
-            xe = np.where(dird[gd], 0.0, np.abs(x[gd]))
+            gd = (conn[e][:, None] * cw + np.arange(cw)[None, :]).ravel()
+            # K drops the Dirichlet columns; Rw takes every column
+            xe = np.abs(x[gd]) if rw else np.where(dird[gd], 0.0, np.abs(x[gd]))
             B += aK0[l * dim + a] @ xe
             X += xe.sum()
         if dird[r]:
-            B = max(B, abs(x[r]))
-        bnd = (nd + 8) * eps * B + delta * Kmax * X
+            # unit diagonal (K); no entry at all (Rw: exactly 0)
+            B = 0.0 if rw else max(B, abs(x[r]))
+            dir_nonzero += rw and y[r] != 0.0
+        bnd = (cw * nn + 8) * eps * B + delta * Kmax * X
         err = float(abs(np.longdouble(y[r]) - ref))
         worst = max(worst, err / bnd if bnd > 0 else (0.0 if err == 0 else np.inf))
         bad += err > bnd
-    return {"rows": int(len(rows)), "classes": int(len(keys)), "delta": float(delta), "delta_elements": 27,
-            "max_err_over_bound": float(worst), "rows_over_bound": int(bad)}
+    out = {"rows": int(len(rows)), "classes": int(len(keys)), "delta": float(delta), "delta_elements": 27,
+           "max_err_over_bound": float(worst), "rows_over_bound": int(bad)}
+    if rw:
+        out["dirichlet_rows_sampled"] = int(dird[rows].sum())
+        out["dirichlet_rows_not_zero"] = int(dir_nonzero)
+    return out
 
 
 def check_solve(pa, np, mat, Ke):
@@ -158,6 +188,90 @@ def check_solve(pa, np, mat, Ke):
     return out
 
 
+def check_solve_matfree(pa, np, dom, mat_e, mat_a):
+    """KleSolver.solve on Taylor-Green from the matrix-free build; the true
+    residual K u - (Rw w + Krhs u_bc) through the assembled matrices."""
+    dim = dom.mesh.dim
+    f = pa.fields.get("taylor_green3d" if dim == 3 else "taylor_green")
+    sol = pa.KleSolver()
+    sol.setMat(mat_e)
+    sol.setUp()
+    vort = mat_e.Rw.createVecRight()
+    vort.setArray(np.asarray(f.vorticity(dom.getFullCoordArray(), 1.0), dtype=np.float64).ravel())
+    vel = sol.getSolution()
+    dom.applyBoundaryConditions(vel, "velocity", 0.0, 0.02)
+    b = mat_a.Rw * vort
+    b.axpy(1.0, mat_a.Krhs * vel)  # vel holds u_bc on the Dirichlet nodes; Krhs reads nothing else
+    sol.solve(vort)
+    ksp = sol.getKSP()
+    r = mat_a.K * vel
+    r.aypx(-1.0, b)
+    return {"operator": ksp.getOperators()[0].spmvKernel(), "iterations": ksp.getIterationNumber(),
+            "reason": ksp.getConvergedReason(), "rtol": 1e-10,
+            "true_rel_residual_assembled": r.norm() / b.norm()}
+
+
+def matfree(a, pa, np, hip, ctx, emit):
+    for mi, spec in enumerate(a.meshes):
+        ne_s, ngl = spec.split(":")
+        nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+        dim = len(nelem)
+        cfg = {"domain": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * dim, "upper": [1.0] * dim}},
+               "boundary-conditions": {"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}}}
+        dom = pa.Domain()
+        dom.configure(cfg)
+        dom.setUp()
+        base = {"nelem": nelem, "ngl": ngl, "dofs": dom.mesh.N * dim, "rounds": a.rounds}
+        mats, t_build, mem = {}, {"assembled": [], "element": []}, {}
+        for rnd in range(a.rounds + 1):  # round 0: untimed (module load, first allocations)
+            for kt in ("assembled", "element"):
+                mats.pop(kt, None)
+                gc.collect()
+                ctx.synchronize()
+                m0 = hip.free_bytes()
+                t0 = time.perf_counter()
+                mat = pa.MatFS()
+                mat.setDomain(dom)
+                mat.build(buildOperators=False, kleType=kt)
+                ctx.synchronize()
+                t1 = time.perf_counter()
+                mats[kt] = mat
+                if rnd:
+                    t_build[kt].append(1e3 * (t1 - t0))
+                    mem[kt] = m0 - hip.free_bytes()
+        for kt in ("assembled", "element"):
+            emit(dict(base, leg="build", kleType=kt, formats=[m.getFormat() for m in mats[kt].kle],
+                      ms=spread(t_build[kt]), device_memory={"bytes_K_Krhs_Rw_Rd": mem[kt]}))
+        ops = {"assembled": mats["assembled"].Rw, "element": mats["element"].Rw}
+        x = ops["element"].createVecRight()
+        x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+        y = ops["element"].createVecLeft()
+        t_prod = {k: [] for k in ops}
+        for _ in range(a.rounds):
+            for label, A in ops.items():
+                for _w in range(20):
+                    A.mult(x, y)
+                ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                t_prod[label].append(1e3 * ms / a.reps)
+        nn = ngl ** dim
+        for label, A in ops.items():
+            flops = (2.0 * dim * nn * (1 if dim == 2 else 3) * nn * dom.mesh.E if label == "element"
+                     else 2.0 * A.getInfo()["nz_used"])
+            emit(dict(base, leg="product_Rw", operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(), flops=flops,
+                      reps=a.reps, us=spread(t_prod[label])))
+        emit(dict(base, leg="ratio_Rw", assembled_over_element={
+            "product": statistics.median(t_prod["assembled"]) / statistics.median(t_prod["element"]),
+            "build": statistics.median(t_build["assembled"]) / statistics.median(t_build["element"]),
+            "device_memory": mem["assembled"] / max(mem["element"], 1)}))
+        if a.check and mi == 0:
+            emit(dict(base, leg="check_product_Rw",
+                      **check_product(pa, np, dom, mats["assembled"], ops["element"], which="Rw")))
+            emit(dict(base, leg="check_solve_matfree",
+                      **check_solve_matfree(pa, np, dom, mats["element"], mats["assembled"])))
+        del ops, mats, x, y, dom
+        gc.collect()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", nargs="+", default=["20,16,16:5", "8,8,6:7"], help="nelem:ngl")
@@ -165,8 +279,12 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--its", type=int, default=50)
     ap.add_argument("--check", action="store_true", help="full-size correctness on the first mesh")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "elem", "elem_ab.jsonl"))
+    ap.add_argument("--matfree", action="store_true",
+                    help="the matrix-free legs: build time and memory per kleType, the Rw product")
+    ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "elem", "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
     import numpy as np
 
     import pynama_amd as pa
@@ -181,6 +299,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.matfree:
+        matfree(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     for mi, spec in enumerate(a.meshes):
         ne_s, ngl = spec.split(":")
         nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
