@@ -56,6 +56,7 @@ enum {
     KLE_DIVERGED_ITS = -3,
     KLE_DIVERGED_DTOL = -4,
     KLE_DIVERGED_BREAKDOWN = -5,
+    KLE_DIVERGED_INDEFINITE_MAT = -8,
     KLE_DIVERGED_NANORINF = -9,
     KLE_CONVERGED_ITERATING = 0
 };
@@ -512,6 +513,14 @@ int kle_ksp_destroy(kle_ksp *k);
 int kle_ksp_set_type(kle_ksp *k, const char *type);      /* "cg" | "gmres" | "preonly" */
 int kle_ksp_set_pc_type(kle_ksp *k, const char *type);   /* "none" | "jacobi" | "lu"   */
 int kle_ksp_set_pc(kle_ksp *k, const char *type);        /* KSPSetPC(PCSetType): same as set_pc_type */
+/* KSPSetTolerances (a negative value / maxit <= 0 keeps the current one;
+ * defaults 1e-5, 1e-50, 1e5, 10000).  The residual norm r_k of every
+ * iteration is tested as KSPConvergedDefault does: NaN/Inf ->
+ * KLE_DIVERGED_NANORINF; r_k <= max(rtol ||b||, atol) -> converged; then
+ * r_k >= dtol ||b|| -> KLE_DIVERGED_DTOL, at iteration 0 too (dtol <= 1
+ * stops every solve there, x = 0); then max_it.  CG, single-reduction and
+ * pipelined CG and GMRES all honour dtol; x is the iterate of the reported
+ * iteration.  Fixed-iteration mode tests none of them. */
 int kle_ksp_set_tolerances(kle_ksp *k, double rtol, double atol, double dtol, int maxit);
 int kle_ksp_set_gmres_restart(kle_ksp *k, int restart);
 /* CG with one reduction per iteration (Chronopoulos-Gear), as PETSc's

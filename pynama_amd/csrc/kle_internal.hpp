@@ -79,8 +79,10 @@ enum Scal {
     S_RHO = 0, S_RHO_OLD, S_PQ, S_ALPHA, S_BETA, S_RR, S_TOL, S_BNORM,
     S_SUM0, S_SUM1, S_SUM2, S_SUM3,  // raw reduction outputs
     S_TMP0, S_TMP1,
-    S_PRHO0, S_PRHO1, S_PALPHA0, S_PALPHA1  // pipelined CG: stage inputs, double-buffered by launch parity
+    S_PRHO0, S_PRHO1, S_PALPHA0, S_PALPHA1,  // pipelined CG: stage inputs, double-buffered by launch parity
+    S_DTOL  // CG: dtol from the host before the start stage, dtol ||b|| after it
 };
+static_assert(S_DTOL < NSCAL, "scalar slots");
 // Device integer state: [0] reason (0 iterating), [1] iterations done,
 // [2] fixed-iteration mode, [3] maxit, [4] arrival ticket of the fused
 // dot + reduction kernel (zeroed with the rest at every solve start, reset

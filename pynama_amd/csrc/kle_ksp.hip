@@ -182,7 +182,7 @@ struct SrStep {
     bool upd;
 };
 __device__ __forceinline__ SrStep sr_step(double g, double rn, double d, double rho_prev, double alpha_prev,
-                                          int its_prev, double tol, int fixed, int maxit, double atol)
+                                          int its_prev, double tol, int fixed, int maxit, double atol, double dtol)
 {
     SrStep s{alpha_prev, 0.0, rho_prev, its_prev + 1, 0, false};
     if (fixed) {
@@ -195,6 +195,9 @@ __device__ __forceinline__ SrStep sr_step(double g, double rn, double d, double 
     } else if (rn <= tol) {
         s.reason = rn <= atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL;
         return s;
+    } else if (rn >= dtol) {  // (dtol ||b||, S_DTOL: KSPConvergedDefault's order -- NaN, converged, diverged)
+        s.reason = KLE_DIVERGED_DTOL;
+        return s;
     } else if (s.its >= maxit) {
         s.reason = KLE_DIVERGED_ITS;
         return s;
@@ -202,7 +205,7 @@ __device__ __forceinline__ SrStep sr_step(double g, double rn, double d, double 
     const double beta = g / rho_prev;
     const double den = d - beta * g / alpha_prev;
     if (den <= 0.0 && !fixed) {
-        s.reason = -8;
+        s.reason = KLE_DIVERGED_INDEFINITE_MAT;
         return s;
     }
     s.beta = beta;
@@ -222,6 +225,7 @@ __device__ void cg_scalars(int stage, double *scal, int *ist, double rtol, doubl
         if (stage == ST_SR_START) {
             scal[S_BNORM] = rn;
             scal[S_TOL] = fmax(rtol * rn, atol);
+            scal[S_DTOL] *= rn;  // (the host left dtol there: dtol ||b|| from here on)
             ist[I_ITS] = 0;
             ist[I_REASON] = 0;
             scal[S_BETA] = 0.0;
@@ -229,12 +233,13 @@ __device__ void cg_scalars(int stage, double *scal, int *ist, double rtol, doubl
             scal[S_ALPHA] = g / d;
             if (!ist[I_FIXED] && rn <= scal[S_TOL]) ist[I_REASON] = rn <= atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL;
             else if (!isfinite(rn)) ist[I_REASON] = KLE_DIVERGED_NANORINF;
-            else if (d <= 0.0 && !ist[I_FIXED]) ist[I_REASON] = -8;
+            else if (!ist[I_FIXED] && rn >= scal[S_DTOL]) ist[I_REASON] = KLE_DIVERGED_DTOL;
+            else if (d <= 0.0 && !ist[I_FIXED]) ist[I_REASON] = KLE_DIVERGED_INDEFINITE_MAT;
             return;
         }
         if (ist[I_REASON] != 0) return;
         const SrStep st = sr_step(g, rn, d, scal[S_RHO], scal[S_ALPHA], ist[I_ITS], scal[S_TOL], ist[I_FIXED],
-                                  ist[I_MAXIT], atol);
+                                  ist[I_MAXIT], atol, scal[S_DTOL]);
         ist[I_ITS] = st.its;
         if (st.reason) ist[I_REASON] = st.reason;
         if (st.upd) {
@@ -249,12 +254,14 @@ __device__ void cg_scalars(int stage, double *scal, int *ist, double rtol, doubl
         const double bn = sqrt(rr);
         scal[S_BNORM] = bn;
         scal[S_TOL] = fmax(rtol * bn, atol);
+        scal[S_DTOL] *= bn;  // (the host left dtol there: dtol ||b|| from here on)
         scal[S_RHO] = rz;
         scal[S_RR] = rr;
         scal[S_BETA] = 0.0;
         ist[I_ITS] = 0;
         ist[I_REASON] = 0;
         if (!ist[I_FIXED] && bn <= scal[S_TOL]) ist[I_REASON] = bn <= atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL;
+        else if (!ist[I_FIXED] && bn >= scal[S_DTOL]) ist[I_REASON] = KLE_DIVERGED_DTOL;
         if (!isfinite(bn)) ist[I_REASON] = KLE_DIVERGED_NANORINF;
         return;
     }
@@ -267,7 +274,7 @@ __device__ void cg_scalars(int stage, double *scal, int *ist, double rtol, doubl
             return;
         }
         if (pq <= 0.0 && !ist[I_FIXED]) {
-            ist[I_REASON] = -8;  // KSP_DIVERGED_INDEFINITE_MAT
+            ist[I_REASON] = KLE_DIVERGED_INDEFINITE_MAT;
             return;
         }
         scal[S_ALPHA] = scal[S_RHO] / pq;
@@ -287,6 +294,7 @@ __device__ void cg_scalars(int stage, double *scal, int *ist, double rtol, doubl
     }
     if (!isfinite(rn)) ist[I_REASON] = KLE_DIVERGED_NANORINF;
     else if (rn <= scal[S_TOL]) ist[I_REASON] = rn <= atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL;
+    else if (rn >= scal[S_DTOL]) ist[I_REASON] = KLE_DIVERGED_DTOL;
     else if (its >= ist[I_MAXIT]) ist[I_REASON] = KLE_DIVERGED_ITS;
 }
 
@@ -364,7 +372,7 @@ __device__ __forceinline__ void sums3(const double *__restrict__ a0, const doubl
 // The scalar inputs of the stage, read by thread 0 at kernel entry so their
 // latency overlaps the partial sums.
 struct StageIn {
-    double prho, palpha, tol, alpha, beta, rho;
+    double prho, palpha, tol, dtol, alpha, beta, rho;
     int pits, fixed, maxit, its;
 };
 __device__ __forceinline__ StageIn stage_inputs(const double *__restrict__ scal, const int *__restrict__ ist, int par)
@@ -373,6 +381,7 @@ __device__ __forceinline__ StageIn stage_inputs(const double *__restrict__ scal,
     in.prho = scal[S_PRHO0 + par];
     in.palpha = scal[S_PALPHA0 + par];
     in.tol = scal[S_TOL];
+    in.dtol = scal[S_DTOL];
     in.alpha = scal[S_ALPHA];
     in.beta = scal[S_BETA];
     in.rho = scal[S_RHO];
@@ -395,7 +404,7 @@ __device__ __forceinline__ bool stage_prologue(int pro, const double (&t)[3], do
         const StageIn in = pre ? *pre : stage_inputs(scal, ist, par);
         if (pro) {
             const SrStep st = sr_step(t[0], sqrt(t[1]), t[2], in.prho, in.palpha, in.pits, in.tol, in.fixed,
-                                      in.maxit, atol);
+                                      in.maxit, atol, in.dtol);
             ab[0] = st.alpha;
             ab[1] = st.beta;
             stop = st.reason != 0;
@@ -647,7 +656,7 @@ __global__ __launch_bounds__(KB) void k_cg_flush(const double *__restrict__ a0, 
     sums3(a0, a1, Ga, a2, G2, t);
     if (threadIdx.x != 0) return;
     const SrStep st = sr_step(t[0], sqrt(t[1]), t[2], scal[S_PRHO0 + par], scal[S_PALPHA0 + par], ist[I_PITS0 + par],
-                              scal[S_TOL], ist[I_FIXED], ist[I_MAXIT], atol);
+                              scal[S_TOL], ist[I_FIXED], ist[I_MAXIT], atol, scal[S_DTOL]);
     scal[S_RR] = t[1];
     ist[I_ITS] = st.its;
     if (st.upd) {
@@ -1267,6 +1276,15 @@ static int true_residual(kle_ksp *k, kle_vec *b, kle_vec *x)
     return 0;
 }
 
+// dtol into its scalar slot ahead of a solve's start stage, which turns it
+// into dtol ||b|| (the stages that test it read the slot: no kernel argument)
+static int put_dtol(kle_ksp *k)
+{
+    kle_ctx *c = k->ctx;
+    KLE_HIP(hipMemcpyAsync(c->d_scal + S_DTOL, &k->dtol, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
 static int solve_cg(kle_ksp *k, kle_vec *b, kle_vec *x)
 {
     kle_ctx *c = k->ctx;
@@ -1276,6 +1294,7 @@ static int solve_cg(kle_ksp *k, kle_vec *b, kle_vec *x)
     const int g = grid_for(n, KB, RED_BLOCKS);
     int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
     KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
+    KLE_TRY(put_dtol(k));
     if (jac)
         hipLaunchKernelGGL(k_cg_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d, k->p->d,
                            c->d_partials);
@@ -1360,6 +1379,7 @@ static int solve_cg_single(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
     KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
     if (!cont) {
+        KLE_TRY(put_dtol(k));
         if (jac)
             hipLaunchKernelGGL(k_sr_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
                                k->u->d, k->p->d, k->s->d, c->d_partials);
@@ -1505,6 +1525,7 @@ static int solve_pipecg(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
     KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
     if (!cont) {
+        KLE_TRY(put_dtol(k));
         if (jac)
             hipLaunchKernelGGL(k_sr_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
                                k->u->d, k->p->d, k->s->d, c->d_partials);
@@ -1674,8 +1695,14 @@ static int solve_gmres(kle_ksp *k, kle_vec *b, kle_vec *x)
     k->its = 0;
     k->reason = 0;
     double rn = bn;
-    if (rn <= tol) {
-        k->reason = rn <= k->atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL;
+    // KSPConvergedDefault's order: NaN/Inf, converged, diverged (dtol ||b||)
+    auto stop = [&](double v) {
+        if (!std::isfinite(v)) return (int)KLE_DIVERGED_NANORINF;
+        if (v <= tol) return (int)(v <= k->atol ? KLE_CONVERGED_ATOL : KLE_CONVERGED_RTOL);
+        if (v >= k->dtol * bn) return (int)KLE_DIVERGED_DTOL;
+        return 0;
+    };
+    if ((k->reason = stop(rn))) {
         k->rnorm = rn;
         return 0;
     }
@@ -1686,7 +1713,7 @@ static int solve_gmres(kle_ksp *k, kle_vec *b, kle_vec *x)
         KLE_TRY(spmv(k->A, k->p, k->V[0], nullptr));
         hipLaunchKernelGGL(k_bmy, dim3(grid_for(n, KB, RED_BLOCKS)), dim3(KB), 0, c->stream, n, b->d, k->V[0]->d);
         KLE_TRY(kle_vec_norm2(k->V[0], &rn));
-        if (rn <= tol) break;
+        if ((k->reason = stop(rn))) break;
         KLE_TRY(kle_vec_scale(k->V[0], 1.0 / rn));
         std::fill(gvec.begin(), gvec.end(), 0.0);
         gvec[0] = rn;
@@ -1710,6 +1737,11 @@ static int solve_gmres(kle_ksp *k, kle_vec *b, kle_vec *x)
             double hn;
             KLE_TRY(kle_vec_norm2(k->V[j + 1], &hn));
             hcol[j + 1] = hn;
+            if (!std::isfinite(hn)) {  // (x stays the last restart's iterate)
+                k->reason = KLE_DIVERGED_NANORINF;
+                k->rnorm = hn;
+                return 0;
+            }
             if (hn > 0) KLE_TRY(kle_vec_scale(k->V[j + 1], 1.0 / hn));
             for (int i = 0; i < j; ++i) {  // apply previous rotations
                 double t = cs[i] * hcol[i] + sn[i] * hcol[i + 1];
@@ -1726,7 +1758,7 @@ static int solve_gmres(kle_ksp *k, kle_vec *b, kle_vec *x)
             for (int i = 0; i <= j; ++i) H[i * m + j] = hcol[i];
             ++k->its;
             rn = std::fabs(gvec[j + 1]);
-            if (rn <= tol || hn == 0) {
+            if ((k->reason = stop(rn)) || hn == 0) {
                 ++j;
                 break;
             }
@@ -1746,7 +1778,7 @@ static int solve_gmres(kle_ksp *k, kle_vec *b, kle_vec *x)
         KLE_HIP(hipGetLastError());
         if (jac) KLE_TRY(kle_vec_pointwise_mult(z, k->dinv, z));
         KLE_TRY(kle_vec_axpy(x, -1.0, z));
-        if (rn <= tol) break;
+        if (k->reason) break;
         if (k->its >= k->maxit) {
             k->reason = KLE_DIVERGED_ITS;
             break;
