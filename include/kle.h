@@ -393,6 +393,41 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * Needs a box mesh with its Dirichlet set, 2-D or 3-D, on one rank;
  * KLE_ERR_SUP for unstructured meshes, no-slip meshes and nranks > 1. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* Element-wise collocation operator of a uniform box mesh: which 0 Curl
+ * [dim_w N x dim N], 1 SrT [dim_s N x dim N], 2 DivSrT [dim N x dim_s N], the
+ * operators kle_assemble_operators assembles, with no stored values:
+ *     y = Winv sum_e S_e^T M_e0 S_e^c x.
+ * Row (l, a) of the element matrix M_e0 has entries only at the nodes on the
+ * dim grid lines through l, so M_e0 x_e is sum-factorised: per element dim
+ * 1-D derivative passes over the gathered x (k_colloc_elem), then inv J, the
+ * coefficient placement of the assembly and c_l = w_l det J; a gather per node
+ * in ascending element order times the inverse lumped weight follows
+ * (k_colloc_gather).  No atomics: bitwise repeatable, and equal to the
+ * assembled product to rounding plus the spread of the element geometry over
+ * the mesh.  c_l, inv J and the derivative table come from the assembly's own
+ * geometry path on the first element's corners.  At creation the dense M_e0 of
+ * the factored tables is compared on the host with the element matrix of the
+ * assembly path (kle_element_ops): exactly 0 off the grid lines, a few ulps on
+ * them, KLE_ERR_STATE otherwise.
+ * Memory: connectivity and incidence tables, N weights and E * RW * ngl^dim
+ * doubles of element results (RW the row components).
+ * The result is a kle_mat of format 2 ("elem").  It supports kle_mat_mult
+ * (KLE_ERR_ARG where y aliases x, KLE_ERR_SIZ for a wrong vector layout),
+ * kle_mat_mult_add, the size / local-size / ownership getters,
+ * kle_mat_get_info (nz_used = 0), kle_mat_spmv_bytes, kle_mat_spmv_kernel and
+ * kle_mat_destroy.  KLE_ERR_SUP: everything the element-wise Rw refuses, and
+ * kle_mat_get_diagonal, kle_ksp_set_operators, kle_mat_copy_dirichlet_rows.
+ * Needs a box mesh on one rank, ngl 2..8; no Dirichlet set is needed and
+ * no-slip box meshes are accepted (the operators carry no boundary rule).
+ * KLE_ERR_SUP for unstructured meshes and nranks > 1, KLE_ERR_ARG for a bad
+ * which. */
+int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* Dense collocation element matrices of local element e as the assembly forms
+ * them, before the nodal weight (parity tests, the creation check above):
+ * Curl_e [dim_w n][dim n], SrT_e [dim_s n][dim n], DivSrT_e [dim n][dim_s n]
+ * (row-major, n = ngl^dim, node-major components) and c_e [n] = w_l det J. */
+int kle_element_ops(kle_ctx *ctx, kle_mesh *m, int64_t e, double *Curl_e, double *SrT_e, double *DivSrT_e,
+                    double *c_e);
 /* dst_i = src_i on the Dirichlet rows of an element-wise operator (its own
  * Dirichlet flags; rows dim N), every other entry of dst untouched; on the
  * context's stream, no synchronisation.  KleSolver uses it after a

@@ -1815,6 +1815,152 @@ static void launch_gather_u(kle_ctx *ctx, const UMeshDev &U, kle_mat *A, const u
                        accum);
 }
 
+// Dense collocation element matrices of one element: the blocks k_ops_gather
+// adds for that element, before the nodal weight, one thread per (row node l,
+// column node m).  Row-major [l R + a][m C + b]; a null output is skipped.
+// Checks only (kle_element_ops, the creation check of kle_colloc.hip).
+template <int DIM>
+__global__ __launch_bounds__(256) void k_ops_element(int ngl, int ne, const double *__restrict__ geo,
+                                                     const double *__restrict__ dh, double *__restrict__ curl,
+                                                     double *__restrict__ srt, double *__restrict__ div)
+{
+    constexpr int DW = DIM == 2 ? 1 : 3, DS = DIM == 2 ? 3 : 6, G1 = 1 + DIM * DIM;
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= (int64_t)ne * ne) return;
+    const int l = (int)(t / ne), m = (int)(t - (int64_t)l * ne);
+    const int oi[3] = {l % ngl, (l / ngl) % ngl, DIM == 3 ? l / (ngl * ngl) : 0};
+    const int oj[3] = {m % ngl, (m / ngl) % ngl, DIM == 3 ? m / (ngl * ngl) : 0};
+    const double *g = geo + (int64_t)l * G1;
+    const double c = g[0];
+    double Hrs[DIM], H[DIM];
+    for (int kk = 0; kk < DIM; ++kk) {
+        bool line = true;
+        for (int j = 0; j < DIM; ++j)
+            if (j != kk) line = line && oj[j] == oi[j];
+        Hrs[kk] = line ? dh[oi[kk] * ngl + oj[kk]] : 0.0;
+    }
+    for (int d = 0; d < DIM; ++d) {
+        double acc = 0.0;
+        for (int kk = 0; kk < DIM; ++kk) acc += g[1 + d * DIM + kk] * Hrs[kk];
+        H[d] = acc;
+    }
+    double C[DW * DIM], S[DS * DIM], D[DIM * DS];
+    for (int q = 0; q < DW * DIM; ++q) C[q] = 0.0;
+    for (int q = 0; q < DS * DIM; ++q) S[q] = D[q] = 0.0;
+    if constexpr (DIM == 3) {
+        C[0 * 3 + 2] += c * H[1];
+        C[0 * 3 + 1] += c * -H[2];
+        C[1 * 3 + 0] += c * H[2];
+        C[1 * 3 + 2] += c * -H[0];
+        C[2 * 3 + 1] += c * H[0];
+        C[2 * 3 + 0] += c * -H[1];
+        S[0 * 3 + 0] += c * H[0];
+        S[1 * 3 + 1] += c * (0.5 * H[0]);
+        S[5 * 3 + 2] += c * (0.5 * H[0]);
+        S[2 * 3 + 1] += c * H[1];
+        S[1 * 3 + 0] += c * (0.5 * H[1]);
+        S[3 * 3 + 2] += c * (0.5 * H[1]);
+        S[4 * 3 + 2] += c * H[2];
+        S[5 * 3 + 0] += c * (0.5 * H[2]);
+        S[3 * 3 + 1] += c * (0.5 * H[2]);
+        D[0 * 6 + 0] += c * H[0];
+        D[0 * 6 + 1] += c * H[1];
+        D[0 * 6 + 5] += c * H[2];
+        D[1 * 6 + 1] += c * H[0];
+        D[1 * 6 + 2] += c * H[1];
+        D[1 * 6 + 3] += c * H[2];
+        D[2 * 6 + 5] += c * H[0];
+        D[2 * 6 + 3] += c * H[1];
+        D[2 * 6 + 4] += c * H[2];
+    } else {
+        C[1] += c * H[0];
+        C[0] += c * -H[1];
+        S[0 * 2 + 0] += c * H[0];
+        S[1 * 2 + 1] += c * (0.5 * H[0]);
+        S[2 * 2 + 1] += c * H[1];
+        S[1 * 2 + 0] += c * (0.5 * H[1]);
+        D[0 * 3 + 0] += c * H[0];
+        D[0 * 3 + 1] += c * H[1];
+        D[1 * 3 + 1] += c * H[0];
+        D[1 * 3 + 2] += c * H[1];
+    }
+    auto put = [&](double *out, const double *blk, int R, int Cc) {
+        if (!out) return;
+        for (int a = 0; a < R; ++a)
+            for (int b = 0; b < Cc; ++b) out[((int64_t)l * R + a) * ne * Cc + (int64_t)m * Cc + b] = blk[a * Cc + b];
+    };
+    put(curl, C, DW, DIM);
+    put(srt, S, DS, DIM);
+    put(div, D, DIM, DS);
+}
+
+// The operator geometry (geo [ne][1 + dim^2]: c_l = w_l det J, inv J) and
+// derivative table (dh [ngl][ngl]) that k_ops_weights and k_ops_gather read,
+// for local element e alone: k_geometry on that element's own corners with
+// the assembly's op point tables.  With outputs given, the element's dense
+// Curl / SrT / DivSrT blocks as well (k_ops_element).
+int element_ops(kle_ctx *ctx, const kle_mesh *m, int64_t e, std::vector<double> &geo, std::vector<double> &dh,
+                std::vector<double> *curl, std::vector<double> *srt, std::vector<double> *div)
+{
+    const int dim = m->dim, dw = dim == 2 ? 1 : 3, ds = dim == 2 ? 3 : 6, nc = 1 << dim, G1 = 1 + dim * dim;
+    const int ne = m->nn(), ngl = m->ngl;
+    const int64_t nel = m->n_local_elems();
+    if (e < 0 || e >= nel) return fail(KLE_ERR_ARG, "element %lld out of local range", (long long)e);
+    DevTables T;
+    KLE_TRY(upload_tables(ctx, ngl, T));
+    if (T.O.np1 != ngl) return fail(KLE_ERR_STATE, "operator points are not the element's nodes");
+    std::vector<double> corners(std::max<int64_t>(nel * nc * dim, 1));
+    KLE_TRY(kle_mesh_get_corners(m, corners.data()));
+    const size_t nC = (size_t)dw * ne * dim * ne, nS = (size_t)ds * ne * dim * ne;
+    double *dX = nullptr, *dgeo = nullptr, *dout[3] = {nullptr, nullptr, nullptr};
+    std::vector<double> *outs[3] = {curl, srt, div};
+    const size_t nout[3] = {nC, nS, nS};
+    auto drop = [&]() {
+        (void)hipFree(dX);
+        (void)hipFree(dgeo);
+        for (double *p : dout) (void)hipFree(p);
+    };
+    bool ok = hipMalloc(&dX, sizeof(double) * nc * dim) == hipSuccess &&
+              hipMalloc(&dgeo, sizeof(double) * ne * G1) == hipSuccess;
+    for (int k = 0; k < 3 && ok; ++k)
+        if (outs[k]) ok = hipMalloc(&dout[k], sizeof(double) * nout[k]) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        drop();
+        return fail(KLE_ERR_MEM, "element operator matrices do not fit");
+    }
+    geo.resize((size_t)ne * G1);
+    dh.resize((size_t)ngl * ngl);
+    hipError_t he = hipMemcpyAsync(dX, corners.data() + e * nc * dim, sizeof(double) * nc * dim, hipMemcpyHostToDevice,
+                                   ctx->stream);
+    if (he == hipSuccess) {
+        const unsigned gq = (unsigned)((ne + 255) / 256), gp = (unsigned)(((int64_t)ne * ne + 255) / 256);
+        if (dim == 2) {
+            hipLaunchKernelGGL(k_geometry<2>, dim3(gq), dim3(256), 0, ctx->stream, (int64_t)1, ngl, T.O, dX, dgeo);
+            if (curl || srt || div)
+                hipLaunchKernelGGL(k_ops_element<2>, dim3(gp), dim3(256), 0, ctx->stream, ngl, ne, dgeo, T.O.dh,
+                                   dout[0], dout[1], dout[2]);
+        } else {
+            hipLaunchKernelGGL(k_geometry<3>, dim3(gq), dim3(256), 0, ctx->stream, (int64_t)1, ngl, T.O, dX, dgeo);
+            if (curl || srt || div)
+                hipLaunchKernelGGL(k_ops_element<3>, dim3(gp), dim3(256), 0, ctx->stream, ngl, ne, dgeo, T.O.dh,
+                                   dout[0], dout[1], dout[2]);
+        }
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
+    if (he == hipSuccess) he = hipMemcpy(geo.data(), dgeo, sizeof(double) * geo.size(), hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(dh.data(), T.O.dh, sizeof(double) * dh.size(), hipMemcpyDeviceToHost);
+    for (int k = 0; k < 3 && he == hipSuccess; ++k)
+        if (outs[k]) {
+            outs[k]->resize(nout[k]);
+            he = hipMemcpy(outs[k]->data(), dout[k], sizeof(double) * nout[k], hipMemcpyDeviceToHost);
+        }
+    drop();
+    if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element operator matrices: %s", hipGetErrorString(he));
+    return 0;
+}
+
 }  // namespace kle
 
 using namespace kle;
@@ -2112,6 +2258,20 @@ int kle_element_kle(kle_ctx *ctx, kle_mesh *m, int64_t e, double *Ke, double *Rw
                 for (int c = 0; c < dw; ++c)
                     Rwe[(size_t)(l * dim + a) * ne * dw + mm * dw + c] = rb[(((size_t)l * ne + mm) * dim + a) * dw + c];
             }
+    return 0;
+}
+
+int kle_element_ops(kle_ctx *ctx, kle_mesh *m, int64_t e, double *Curl_e, double *SrT_e, double *DivSrT_e, double *c_e)
+{
+    KLE_ARG(ctx && m && Curl_e && SrT_e && DivSrT_e && c_e, "null arg");
+    KLE_HIP(hipSetDevice(ctx->device));
+    std::vector<double> geo, dh, mc, ms, md;
+    KLE_TRY(element_ops(ctx, m, e, geo, dh, &mc, &ms, &md));
+    std::copy(mc.begin(), mc.end(), Curl_e);
+    std::copy(ms.begin(), ms.end(), SrT_e);
+    std::copy(md.begin(), md.end(), DivSrT_e);
+    const int G1 = 1 + m->dim * m->dim;
+    for (int l = 0; l < m->nn(); ++l) c_e[l] = geo[(size_t)l * G1];
     return 0;
 }
 

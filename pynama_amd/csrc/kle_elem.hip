@@ -230,8 +230,8 @@ __global__ __launch_bounds__(256) void k_elem_copy_dirichlet(int64_t n, int dim,
 
 // Every index the device tables hold, checked on the host before upload: a
 // bad table is an error code, never an out-of-range access.
-static int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E,
-                         int nn, int maxinc)
+int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E, int nn,
+                  int maxinc)
 {
     if ((int64_t)conn.size() != E * nn || (int64_t)inc.size() != N * maxinc)
         return fail(KLE_ERR_SIZ, "element operator: table sizes do not match the mesh");

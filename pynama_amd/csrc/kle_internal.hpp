@@ -197,13 +197,15 @@ struct kle_vec {
 };
 
 namespace kle {
-struct ElemOp;  // kle_elem.hip: the element-wise operator of a uniform box mesh
+struct ElemOp;    // kle_elem.hip: the element-wise operator of a uniform box mesh
+struct CollocOp;  // kle_colloc.hip: an element-wise collocation operator (Curl, SrT, DivSrT)
 }
 
 struct kle_mat {
     kle_ctx *ctx = nullptr;
     int kind = 0;  // 0 node-block, 1 scalar AIJ, 2 element-wise (no stored values: elem)
     kle::ElemOp *elem = nullptr;  // kind 2
+    kle::CollocOp *colloc = nullptr;  // kind 2, instead of elem: Curl / SrT / DivSrT (kle_colloc.hip)
     int halo_overlap = 1;          // N>1: interior rows run while the halo is in flight
     int64_t int_lo = 0, int_hi = 0;  // rows [int_lo, int_hi) read no ghost entries
     int64_t row_lat[3] = {1, 1, 1};  // lattice of the owned rows (x, y, z extents)
@@ -412,6 +414,15 @@ int elem_diagonal(const kle_mat *A, kle_vec *d);
 void elem_drop(kle_mat *A);
 double elem_spmv_bytes(const kle_mat *A);
 std::string elem_kernel_name(const kle_mat *A);
+int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E, int nn,
+                  int maxinc);
+// element-wise collocation operators (kle_colloc.hip; kle_mat kind 2 with colloc set)
+int element_ops(kle_ctx *ctx, const kle_mesh *m, int64_t e, std::vector<double> &geo, std::vector<double> &dh,
+                std::vector<double> *curl, std::vector<double> *srt, std::vector<double> *div);  // kle_assemble.hip
+int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+void colloc_drop(kle_mat *A);
+double colloc_spmv_bytes(const kle_mat *A);
+std::string colloc_kernel_name(const kle_mat *A);
 // kind 2 holds no assembled values: the calls that need them end here
 #define KLE_NO_ELEM(A, what)                                                                              \
     do {                                                                                                  \

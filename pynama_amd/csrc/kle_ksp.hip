@@ -1956,6 +1956,8 @@ int kle_ksp_set_fixed_iterations(kle_ksp *k, int n)
 int kle_ksp_set_operators(kle_ksp *k, kle_mat *A)
 {
     KLE_ARG(k && A, "null arg");
+    if (A->kind == 2 && A->colloc)
+        return fail(KLE_ERR_SUP, "KSP: an element-wise collocation operator is no system matrix");
     KLE_ARG(A->m_global == A->n_global, "KSP needs a square operator");
     k->A = A;
     k->setup = false;

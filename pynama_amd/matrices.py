@@ -26,6 +26,16 @@ def kle_mat_type(kleType=None):
     return kleType
 
 
+def kle_op_type(opType=None):
+    """The form of Curl, SrT and DivSrT: the keyword, else -kle_op_type, else
+    "assembled"; anything but assembled | element raises Error 62."""
+    if opType is None:
+        opType = Options().getString("kle_op_type", "assembled")
+    if opType not in ("assembled", "element"):
+        raise Error(62, f"-kle_op_type {opType}: assembled | element")
+    return opType
+
+
 class MatFS:
     bcType = "FS"
 
@@ -37,16 +47,20 @@ class MatFS:
     def setDomain(self, dom):
         self.dom = dom
 
-    def build(self, buildKLE=True, buildOperators=True, kleType=None):
+    def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None):
         """kleType (default: -kle_mat_type, default "assembled"): "element"
         builds K, Krhs and Rw as element-wise operators and assembles nothing
-        (uniform box meshes on one rank; anything else raises Error 56)."""
+        (uniform box meshes on one rank; anything else raises Error 56).
+        opType (default: -kle_op_type, default "assembled"): "element" does the
+        same for Curl, SrT and DivSrT; with both, nothing at all is assembled."""
         if self.dom.getBoundaryType() != "FS":
             raise Error(56, "MatFS needs free-slip (Dirichlet) boundaries")
+        kleType = kle_mat_type(kleType) if buildKLE else kleType
+        opType = kle_op_type(opType) if buildOperators else opType
         if buildKLE:
-            self.buildFS(kle_mat_type(kleType))
+            self.buildFS(kleType)
         if buildOperators:
-            self.buildOperators()
+            self.buildOperators(opType)
 
     def buildFS(self, kleType="assembled"):
         ctx = get_ctx()
@@ -104,12 +118,13 @@ class MatFS:
             self._elemRw = Mat.createKLEElement(self.dom.getMesh(), "Rw")
         return self._elemRw
 
-    def buildOperators(self):
-        """Curl / SrT / DivSrT on the device (mat_fs.py:194-201): assembled,
-        whatever the kleType."""
+    def buildOperators(self, opType=None):
+        """Curl / SrT / DivSrT on the device (mat_fs.py:194-201): assembled
+        whatever the kleType, unless opType (default: -kle_op_type) is
+        "element"."""
         self.operator = Operators()
         self.operator.setDimensions(self.dom.getDimensions())
-        self.operator.build(self.dom.getMesh())
+        self.operator.build(self.dom.getMesh(), opType)
 
     def getOperators(self):
         return self.operator
@@ -131,15 +146,19 @@ class MatNS(MatFS):
         self.Kfs = self.Krhsfs = self.Rwfs = self.Rdfs = None
         self._Ksum = None
 
-    def build(self, buildKLE=True, buildOperators=True, kleType=None):
+    def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None):
+        """opType "element" (default: -kle_op_type): Curl, SrT and DivSrT as
+        element-wise operators, which carry no boundary rule; the no-slip KLE
+        matrices themselves have no element-wise form."""
         if kle_mat_type(kleType) == "element":
             raise Error(56, "-kle_mat_type element: no-slip matrices have no element-wise form")
         if self.dom.getBoundaryType() != "NS":
             raise Error(56, "MatNS needs no-slip boundaries")
+        opType = kle_op_type(opType) if buildOperators else opType
         if buildKLE:
             self.buildNS()
         if buildOperators:
-            self.buildOperators()
+            self.buildOperators(opType)
 
     def buildNS(self):
         ctx = get_ctx()
@@ -165,7 +184,9 @@ class Operators:
     [dim N x dim_s N], each left-scaled by the inverse lumped nodal weight.
     Assembled in one device pass (libkle kle_assemble_operators) instead of
     the per-cell setValues loop; same pattern (explicit zeros kept) and the
-    same ascending-cell ADD order."""
+    same ascending-cell ADD order.  With opType "element" (-kle_op_type
+    element) nothing is assembled: the three are element-wise operators
+    (Mat.createOperatorElement; uniform box meshes on one rank)."""
 
     def __init__(self):
         self.Curl = self.SrT = self.DivSrT = None
@@ -173,7 +194,12 @@ class Operators:
     def setDimensions(self, dims):
         self.dim, self.dim_w, self.dim_s = dims
 
-    def build(self, mesh):
+    def build(self, mesh, opType=None):
+        if kle_op_type(opType) == "element":
+            self.Curl, self.SrT, self.DivSrT = (Mat.createOperatorElement(mesh, n) for n in ("Curl", "SrT", "DivSrT"))
+            for m, n in ((self.Curl, "Curl"), (self.SrT, "SrT"), (self.DivSrT, "DivSrT")):
+                m.setName(n)
+            return
         ctx = get_ctx()
         hc, hs, hd = C.c_void_p(), C.c_void_p(), C.c_void_p()
         call("kle_assemble_operators", ctx.h, mesh._h, C.byref(hc), C.byref(hs), C.byref(hd))

@@ -356,6 +356,28 @@ class Mat:
         m.setName("element " + which)
         return m
 
+    @classmethod
+    def createOperatorElement(cls, mesh, which="Curl"):
+        """Element-wise Curl, SrT or DivSrT of a uniform box mesh
+        (kle_mat_create_operator_element): sum-factorised products from the
+        mesh's one element, no assembled values.  Curl is [dim_w N x dim N], SrT
+        [dim_s N x dim N], DivSrT [dim N x dim_s N].  mult, *, multAdd,
+        createVecLeft/Right, the size getters, getInfo and spmvKernel work;
+        calls that need stored values, getDiagonal and KSP.setOperators raise
+        Error 56, as do unstructured and multi-rank meshes.  No Dirichlet set
+        is needed and no-slip box meshes are accepted."""
+        kinds = {"Curl": 0, "SrT": 1, "DivSrT": 2}
+        if which not in kinds:
+            raise Error(62, f"createOperatorElement: which must be 'Curl', 'SrT' or 'DivSrT', not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_operator_element", ctx.h, mesh._h, kinds[which], C.byref(h))
+        dim_w, dim_s = (1, 3) if mesh.dim == 2 else (3, 6)
+        rbs, cbs = {"Curl": (dim_w, mesh.dim), "SrT": (dim_s, mesh.dim), "DivSrT": (mesh.dim, dim_s)}[which]
+        m = cls._wrap(h, ctx, mesh, rbs, cbs)
+        m.setName("element " + which)
+        return m
+
     def copyDirichletRows(self, src, dst):
         """dst[i] = src[i] on the Dirichlet rows of an element-wise operator,
         nothing else touched (kle_mat_copy_dirichlet_rows)."""

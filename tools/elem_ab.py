@@ -30,7 +30,27 @@ assembled Rw) and one KleSolver.solve on Taylor-Green from the matrix-free
 build, its true residual K u - (Rw w + Krhs u_bc) formed through the assembled
 matrices.
 
-  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check] [--matfree]
+With --operators the legs are those of the element-wise collocation operators
+(Mat.createOperatorElement, kle_colloc.hip; records to
+profiles/elem/operators.jsonl), per mesh and in one process, opType assembled
+and element alternating:
+
+  build_operators  wall time of Operators.build and the device memory Curl, SrT
+                   and DivSrT hold (hipMemGetInfo before / after), after one
+                   untimed build of each kind
+  product_<op>     --reps products of Curl, SrT and DivSrT, timed as above
+  chain            the evalRHS chain without the KLE solve: computeVtensV, SrT,
+                   scale, axpy, DivSrT, scale, Curl
+
+and with --check (first mesh) the product bound of tests/test_gpu_colloc.py on
+the row sample over all incidence classes (reference rows from the assembled
+operators, element matrices from the oracle's Element.ops on the mesh's own
+corners, delta over the 27 first / middle / last elements per axis).  With
+--config4 instead: one BaseProblem at config 4's stated size ([18,18,18],
+ngl 7) under -kle_mat_type element -kle_op_type element, one evalRHS, its time
+and the device memory held.
+
+  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check] [--matfree | --operators [--config4]]
 """
 import argparse
 import ctypes as C
@@ -272,6 +292,250 @@ def matfree(a, pa, np, hip, ctx, emit):
         gc.collect()
 
 
+OPS = ("Curl", "SrT", "DivSrT")
+
+
+def op_shape(dim, nm):
+    dw, ds = (1, 3) if dim == 2 else (3, 6)
+    return {"Curl": (dw, dim), "SrT": (ds, dim), "DivSrT": (dim, ds)}[nm]
+
+
+def check_product_ops(pa, np, dom, asm, elem, nrows=4096):
+    """tests/test_gpu_colloc.py's bound on a sample of rows of the full-size
+    mesh, per operator."""
+    from oracle import oracle as O
+    mesh, dim, ngl = dom.mesh, dom.mesh.dim, dom.mesh.ngl
+    nn, E, N = ngl ** dim, mesh.E, mesh.N
+    eps = np.finfo(np.float64).eps
+    conn = mesh.conn()
+    ninc = np.bincount(conn.ravel(), minlength=N)
+    ne = list(mesh.nelem) + [1] * (3 - dim)
+    om = O.BoxMesh(dim, ne[:dim], [0.0] * dim, [1.0] * dim, ngl)  # the tool's meshes are unit boxes
+    perm = np.array([np.where(conn[0] == c)[0][0] for c in om.conn()[0]])
+    del om
+    el = O.Element(ngl, dim)
+    corners = mesh.corners()
+
+    def ops(e):
+        SrT, Div, Curl, W = el.ops(corners[e].ravel())
+        out = {}
+        for nm, M in (("Curl", Curl), ("SrT", SrT), ("DivSrT", Div)):
+            R, Cc = op_shape(dim, nm)
+            pr = (perm[:, None] * R + np.arange(R)[None, :]).ravel()
+            pc = (perm[:, None] * Cc + np.arange(Cc)[None, :]).ravel()
+            T = np.zeros_like(M)
+            T[np.ix_(pr, pc)] = M
+            out[nm] = T
+        c = np.zeros(nn)
+        c[perm] = W
+        return out, c
+
+    M0, c0 = ops(0)
+    pos = [sorted({0, n // 2, n - 1}) for n in ne]
+    delta, delta_w = {nm: 0.0 for nm in OPS}, 0.0
+    for ez in pos[2]:
+        for ey in pos[1]:
+            for ex in pos[0]:
+                e = ex + ne[0] * (ey + ne[1] * ez)
+                if e:
+                    Me, ce = ops(e)
+                    for nm in OPS:
+                        delta[nm] = max(delta[nm], np.abs(Me[nm] - M0[nm]).max() / np.abs(M0[nm]).max())
+                    delta_w = max(delta_w, np.abs(ce - c0).max() / np.abs(c0).max())
+    W = np.zeros(N)
+    np.add.at(W, conn, np.broadcast_to(c0[None, :], conn.shape))
+    winv = 1.0 / W
+    rng = np.random.default_rng(7)
+    keys = np.unique(ninc)
+    order = np.argsort(conn.ravel(), kind="stable")
+    start = np.concatenate([[0], np.cumsum(ninc)])
+    out = {"classes": int(len(keys)), "delta_elements": 27, "delta_w": float(delta_w)}
+    for nm in OPS:
+        R, Cc = op_shape(dim, nm)
+        per = max(1, (nrows // R) // len(keys) + 1)
+        nodes = np.concatenate([rng.permutation(np.flatnonzero(ninc == k))[:per] for k in keys])
+        rows = (nodes[:, None] * R + np.arange(R)[None, :]).ravel()[:nrows]
+        A, Ae = getattr(asm, nm), getattr(elem, nm)
+        x = np.random.default_rng(20240611).uniform(-1, 1, N * Cc)
+        xv = Ae.createVecRight()
+        xv.setArray(x)
+        y = (Ae * xv).getArray()
+        aM, Mmax = np.abs(M0[nm]), np.abs(M0[nm]).max()
+        n = Cc * (dim * (ngl - 1) + 1) + 2 ** dim + 8
+        worst, bad = 0.0, 0
+        for r in rows:
+            cols, vals = A.getRow(int(r))
+            ref = np.sum(vals.astype(np.longdouble) * x[cols].astype(np.longdouble))
+            node, a = divmod(int(r), R)
+            B = X = 0.0
+            for t in order[start[node]:start[node + 1]]:
+                e, l = divmod(int(t), nn)
+                xe = np.abs(x[(conn[e][:, None] * Cc + np.arange(Cc)[None, :]).ravel()])
+                B += aM[l * R + a] @ xe
+                X += xe.sum()
+            B *= winv[node]
+            bnd = n * eps * B + delta[nm] * Mmax * X * winv[node] + 2 * delta_w * B
+            err = float(abs(np.longdouble(y[r]) - ref))
+            worst = max(worst, err / bnd if bnd > 0 else (0.0 if err == 0 else np.inf))
+            bad += err > bnd
+        out[nm] = {"rows": int(len(rows)), "delta": float(delta[nm]), "max_err_over_bound": float(worst),
+                   "rows_over_bound": int(bad)}
+    return out
+
+
+def eval_rhs_chain(call, prob, vel, rhs, f):
+    """BaseProblem.evalRHS after the KLE solve."""
+    op = prob.operator
+    call("kle_vec_tensor_square", vel._h, prob.dim, prob._VtensV._h)
+    op.SrT.mult(vel, prob._Aux1)
+    prob._Aux1 *= (2.0 * prob.mu)
+    prob._Aux1.axpy(-1.0 * prob.rho, prob._VtensV)
+    op.DivSrT.mult(prob._Aux1, rhs)
+    rhs.scale(1 / prob.rho)
+    op.Curl.mult(rhs, f)
+
+
+class Chain:
+    """What evalRHS's chain reads of a BaseProblem, around one Operators."""
+
+    def __init__(self, op, dim):
+        self.operator, self.dim, self.mu, self.rho = op, dim, 0.01, 0.5
+        self._VtensV = op.SrT.createVecLeft()
+        self._Aux1 = self._VtensV.duplicate()
+
+
+def operators(a, pa, np, hip, ctx, emit):
+    from pynama_amd._lib import call
+    from pynama_amd.matrices import Operators
+    for mi, spec in enumerate(a.meshes):
+        ne_s, ngl = spec.split(":")
+        nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+        dim = len(nelem)
+        cfg = {"domain": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * dim, "upper": [1.0] * dim}},
+               "boundary-conditions": {"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}}}
+        dom = pa.Domain()
+        dom.configure(cfg)
+        dom.setUp()
+        base = {"nelem": nelem, "ngl": ngl, "nodes": dom.mesh.N, "rounds": a.rounds}
+        kinds = ("assembled", "element")
+        built, t_build, mem = {}, {k: [] for k in kinds}, {}
+        for rnd in range(a.rounds + 1):  # round 0: untimed (module load, first allocations)
+            for ot in kinds:
+                built.pop(ot, None)
+                gc.collect()
+                ctx.synchronize()
+                m0 = hip.free_bytes()
+                t0 = time.perf_counter()
+                op = Operators()
+                op.setDimensions(dom.getDimensions())
+                op.build(dom.getMesh(), ot)
+                ctx.synchronize()
+                t1 = time.perf_counter()
+                built[ot] = op
+                if rnd:
+                    t_build[ot].append(1e3 * (t1 - t0))
+                    mem[ot] = m0 - hip.free_bytes()
+        for ot in kinds:
+            emit(dict(base, leg="build_operators", opType=ot, formats=[getattr(built[ot], n).getFormat() for n in OPS],
+                      ms=spread(t_build[ot]), device_memory={"bytes_Curl_SrT_DivSrT": mem[ot]}))
+        ratios = {}
+        for nm in OPS:
+            ops = {ot: getattr(built[ot], nm) for ot in kinds}
+            x = ops["element"].createVecRight()
+            x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+            y = ops["element"].createVecLeft()
+            t_prod = {k: [] for k in kinds}
+            for _ in range(a.rounds):
+                for label, A in ops.items():
+                    for _w in range(20):
+                        A.mult(x, y)
+                    ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                    t_prod[label].append(1e3 * ms / a.reps)
+            for label, A in ops.items():
+                emit(dict(base, leg="product_" + nm, operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                          reps=a.reps, us=spread(t_prod[label]),
+                          tb_per_s=A.spmvBytes() / statistics.median(t_prod[label]) * 1e-6))
+            ratios[nm] = {"assembled_over_element": statistics.median(t_prod["assembled"]) / statistics.median(t_prod["element"]),
+                          "element_faster_beyond_spread": bool(max(t_prod["element"]) < min(t_prod["assembled"]))}
+        chains = {ot: Chain(built[ot], dim) for ot in kinds}
+        vel = built["element"].SrT.createVecRight()
+        f = pa.fields.get("taylor_green3d" if dim == 3 else "taylor_green")
+        vel.setArray(np.asarray(f.velocity(dom.getFullCoordArray(), 1.0), dtype=np.float64).ravel())
+        rhs, fo = vel.duplicate(), built["element"].Curl.createVecLeft()
+        t_chain, outs = {k: [] for k in kinds}, {}
+        for _ in range(a.rounds):
+            for label, ch in chains.items():
+                for _w in range(10):
+                    eval_rhs_chain(call, ch, vel, rhs, fo)
+                ms = hip.timed_ms(lambda: [eval_rhs_chain(call, ch, vel, rhs, fo) for _r in range(a.reps)])
+                t_chain[label].append(ms / a.reps)
+                outs[label] = fo.getArray().copy()
+        for label in kinds:
+            emit(dict(base, leg="chain", operator=label, steps="computeVtensV, SrT, scale, axpy, DivSrT, scale, Curl",
+                      reps=a.reps, ms=spread(t_chain[label])))
+        ratios["chain"] = {"assembled_over_element": statistics.median(t_chain["assembled"]) / statistics.median(t_chain["element"]),
+                           "element_faster_beyond_spread": bool(max(t_chain["element"]) < min(t_chain["assembled"])),
+                           "max_abs_difference_of_f": float(np.abs(outs["element"] - outs["assembled"]).max()),
+                           "max_abs_f": float(np.abs(outs["assembled"]).max())}
+        ratios["build"] = {"assembled_over_element": statistics.median(t_build["assembled"]) / statistics.median(t_build["element"])}
+        ratios["device_memory"] = {"assembled_over_element": mem["assembled"] / max(mem["element"], 1)}
+        emit(dict(base, leg="ratio_operators", **ratios))
+        if a.check and mi == 0:
+            emit(dict(base, leg="check_product_operators",
+                      **check_product_ops(pa, np, dom, built["assembled"], built["element"])))
+        del chains, built, vel, rhs, fo, dom
+        gc.collect()
+
+
+def config4(a, pa, np, hip, ctx, emit):
+    """One BaseProblem at config 4's stated size with nothing assembled."""
+    from pynama_amd._lib import call
+    from pynama_amd.petsc import Options
+    nelem, ngl = [18, 18, 18], 7
+    bc = {"custom-func": {"name": "taylor_green3d"}}
+    cfg = {"name": "config4", "material-properties": {"rho": 0.5, "mu": 0.01},
+           "domain": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * 3, "upper": [1.0] * 3}},
+           "boundary-conditions": bc, "initial-conditions": bc}
+    ctx.synchronize()
+    m0 = hip.free_bytes()
+    opts = Options()
+    opts.setValue("kle_mat_type", "element")
+    opts.setValue("kle_op_type", "element")
+    t0 = time.perf_counter()
+    try:
+        prob = pa.BaseProblem(cfg)
+        prob.setUp()
+        prob.setUpSolver()
+    finally:
+        opts.delValue("kle_mat_type")
+        opts.delValue("kle_op_type")
+    ctx.synchronize()
+    t1 = time.perf_counter()
+    m1 = hip.free_bytes()
+    fo = prob.operator.Curl.createVecLeft()
+    prob.evalRHS(None, 0.0, prob.vort, fo)
+    ctx.synchronize()
+    t2 = time.perf_counter()
+    ksp = prob.solverKLE.getKSP()
+    vel = prob.solverKLE.getSolution()
+    rhs = vel.duplicate()
+    for _w in range(3):
+        eval_rhs_chain(call, prob, vel, rhs, fo)
+    chain_ms = [hip.timed_ms(lambda: [eval_rhs_chain(call, prob, vel, rhs, fo) for _r in range(20)]) / 20
+                for _ in range(a.rounds)]
+    out = fo.getArray()
+    emit({"leg": "config4_eval_rhs", "nelem": nelem, "ngl": ngl, "nodes": prob.dom.mesh.N,
+          "options": "-kle_mat_type element -kle_op_type element",
+          "formats": {n: getattr(prob.operator, n).getFormat() for n in OPS} | {"K": prob.mat.K.getFormat()},
+          "whole_eval_rhs_ran_on_one_gpu": bool(np.all(np.isfinite(out))),
+          "setup_wall_s": t1 - t0, "eval_rhs_wall_s": t2 - t1,
+          "kle_iterations": ksp.getIterationNumber(), "kle_reason": ksp.getConvergedReason(),
+          "chain_ms": spread(chain_ms),
+          "device_memory": {"bytes_after_setup": m0 - m1, "bytes_after_eval_rhs": m0 - hip.free_bytes()},
+          "assembled_counterpart": "not built: by SURVEY section 7's entry counts the assembled Curl, SrT and DivSrT "
+                                   "hold about 320 GB at this size, more than one MI355X's 288 GB"})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", nargs="+", default=["20,16,16:5", "8,8,6:7"], help="nelem:ngl")
@@ -281,10 +545,16 @@ def main():
     ap.add_argument("--check", action="store_true", help="full-size correctness on the first mesh")
     ap.add_argument("--matfree", action="store_true",
                     help="the matrix-free legs: build time and memory per kleType, the Rw product")
-    ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree)")
+    ap.add_argument("--operators", action="store_true",
+                    help="the collocation-operator legs: build, products and the evalRHS chain per opType")
+    ap.add_argument("--config4", action="store_true",
+                    help="with --operators: one evalRHS at [18,18,18] ngl 7 with nothing assembled, instead of the legs")
+    ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree, "
+                                                "operators.jsonl with --operators)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "elem", "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "elem", "operators.jsonl" if a.operators else
+                             "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
     import numpy as np
 
     import pynama_amd as pa
@@ -299,6 +569,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.operators:
+        (config4 if a.config4 else operators)(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     if a.matfree:
         matfree(a, pa, np, hip, ctx, emit)
         fout.close()
