@@ -496,9 +496,22 @@ int kle_mat_is_structured(const kle_mat *A, int *on);
  * otherwise KLE_ERR_SUP.  Collective at N > 1.  The full
  * storage stays (getRow, CSR export); any value change (diagonalScale, axpy,
  * setValues/assemble) drops the symmetric copy.  kle_assemble_kle turns it on
- * for K (tuning "spmv_sym", "spmv_sym_min_rows").  Results agree with the
- * full-storage SpMV to rounding (a different summation order); with the
- * default "spmv_sym_det" they are bitwise reproducible run to run. */
+ * for K (tuning "spmv_sym", "spmv_sym_min_rows").  With the default
+ * "spmv_sym_det" results are bitwise reproducible run to run.
+ * Accuracy (tests/test_gpu_sym_ref.py): the assembled K equals its transpose
+ * bit for bit (k_gather reads one triangle of every element matrix), so the
+ * stored triangle is the exported matrix.  Norm-wise y agrees with the
+ * full-storage product at fp64 level.  Component-wise, with u = 2^-53,
+ *     |y_i - (K x)_i| <= O(u) (|K||x|)_i + nT_i 2^(E-62):
+ * row i's direct sum is fp64; each of the nT_i node blocks transposed into it
+ * enters an int64 sum rounded to q = 2^(E-61), 2^E > (the part's bound <=
+ * 4 ||K||inf) x (max|x| over the part's region), E <= log2(16 ||K||inf
+ * ||x||inf).  The sums are exact integer sums (order-free), not exact
+ * products: where x spans many decades the quantum follows the region's
+ * largest entry, and a row whose own terms are small sees it (one entry 1e8
+ * among O(1): 1e-8 relative on the worst row, 4e-15 norm-wise).  The scale
+ * is two normal factors: subnormal x is not flushed, sums near DBL_MAX do not
+ * wrap (a transposed term that itself overflows is not detected). */
 int kle_mat_set_symmetric(kle_mat *A, int on);
 int kle_mat_get_symmetric(const kle_mat *A, int *on);
 /* The brick decomposition of A's symmetric storage (kle_brick.hip; 0 bricks:

@@ -501,6 +501,30 @@ struct MeshDev {
     int64_t node_begin, ext_begin, elem_begin;
 };
 
+// Entry t = a C + b of K_e's block (li, lj), read from one triangle of K_e.
+// Block (l, m) and block (m, l) transposed are the same numbers in exact
+// arithmetic but not in fp64: the element kernels scale the l side by the
+// quadrature weight, (c g_l) g_m against (c g_m) g_l.  K's gather takes both
+// from the block with l < m (on l == m from the entry with a <= b), and sums
+// entry (i, j) and entry (j, i) over the same cells in the same order, so the
+// assembled K equals its transpose bit for bit: the symmetric storages, which
+// keep the upper triangle alone, give the product of the very matrix that
+// the full storage holds and getValuesCSR exports, not of a neighbour at
+// rounding distance (whose noise-level entries differ by 100 %).
+template <int R, int C>
+__device__ __forceinline__ double sym_elem_entry(const double *__restrict__ Ee, int ne, int li, int lj, int t)
+{
+    static_assert(R == C, "K's blocks are square");
+    int a = t / C, b = t - a * C;
+    if (li > lj || (li == lj && a > b)) {
+        const int s = a;
+        a = b;
+        b = s;
+    }
+    const int lo = min(li, lj), hi = max(li, lj);
+    return Ee[((int64_t)lo * ne + hi) * (R * C) + a * C + b];
+}
+
 // MODE 0: K (free cols, +K_e), 1: Krhs (Dirichlet cols, -K_e), 2: Rw (+Rw_e)
 template <int R, int C, int MODE>
 __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const int *__restrict__ rowptr,
@@ -565,9 +589,15 @@ __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const 
                     if (!in || e < eb0 || e >= eb1) continue;
                     const int li = oi[0] + ngl * (oi[1] + ngl * oi[2]);
                     const int lj = oj[0] + ngl * (oj[1] + ngl * oj[2]);
-                    const double *blk = Eblk + (((e - eb0) * ne + li) * (int64_t)ne + lj) * (R * C);
+                    if constexpr (MODE == 0 && R == C) {
+                        const double *Ee = Eblk + (e - eb0) * ne * (int64_t)ne * (R * C);
 #pragma unroll
-                    for (int t = 0; t < R * C; ++t) acc[t] += (MODE == 1) ? -blk[t] : blk[t];
+                        for (int t = 0; t < R * C; ++t) acc[t] += sym_elem_entry<R, C>(Ee, ne, li, lj, t);
+                    } else {
+                        const double *blk = Eblk + (((e - eb0) * ne + li) * (int64_t)ne + lj) * (R * C);
+#pragma unroll
+                        for (int t = 0; t < R * C; ++t) acc[t] += (MODE == 1) ? -blk[t] : blk[t];
+                    }
                 }
 #pragma unroll
         for (int a = 0; a < R; ++a)
@@ -1659,10 +1689,16 @@ __global__ __launch_bounds__(64) void k_gather_u(UMeshDev U, int64_t nrows, cons
             for (int lj = lane; lj < ne; lj += 64) {
                 const int pos = find_col(cols, w0, w0 + wn, ce[lj]);
                 if (pos < 0) continue;
-                const double *blk = Eblk + (((int64_t)(e - eb0) * ne + li) * ne + lj) * RC;
                 double *a = acc + (pos - w0) * RC;
+                if constexpr (MODE == 0 && R == C) {  // (K: one triangle of K_e, sym_elem_entry)
+                    const double *Ee = Eblk + (int64_t)(e - eb0) * ne * ne * RC;
 #pragma unroll
-                for (int t = 0; t < RC; ++t) a[t] += (MODE == 1 || MODE == 4) ? -blk[t] : blk[t];
+                    for (int t = 0; t < RC; ++t) a[t] += sym_elem_entry<R, C>(Ee, ne, li, lj, t);
+                } else {
+                    const double *blk = Eblk + (((int64_t)(e - eb0) * ne + li) * ne + lj) * RC;
+#pragma unroll
+                    for (int t = 0; t < RC; ++t) a[t] += (MODE == 1 || MODE == 4) ? -blk[t] : blk[t];
+                }
             }
             __syncthreads();
         }

@@ -378,7 +378,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // the brick's scale: 2^(61 - E), 2^E > (its sums' bound, k_brick_bound) x
     // max |x|, as two factors S1 S2 (and 1 / S as T1 T2), each a normal
     // double, so that x near the bottom of the exponent range (2^(61 - E) >
-    // 2^1023) keeps its 61 bits too
+    // 2^1023) keeps its 61 bits too, and sums near the top of it (bound x
+    // max |x| >= 2^1024 while every sum itself is finite) stay below 2^61
     double S1 = 1.0, S2 = 1.0, T1 = 1.0, T2 = 1.0;
     {
         double m = 0.0, nb = 0.0;
@@ -393,8 +394,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         } else if (m > 0.0) {
             int em;
             (void)frexp(m, &em);
-            const int E = min(max(eb + em, -1070), 1020);
-            const int e1 = min(61 - E, 1000), e2 = 61 - E - e1;
+            const int E = max(eb + em, -1070);  // (<= 2048: no clamp above, or sums near DBL_MAX would pass 2^61)
+            const int e1 = max(min(61 - E, 1000), -1000), e2 = 61 - E - e1;
             S1 = ldexp(1.0, e1);
             S2 = ldexp(1.0, e2);
             T1 = ldexp(1.0, -e1);
@@ -415,9 +416,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         // the row's direct sum (fixed-order DPP, fp64), one writer, into y --
         // the gather adds the bricks' transposed sums to it (8 MB of stores
         // at config 2: the only ones before the end)
-        // DOT: each lane's part of the row's sum times the row's x, c (the
-        // lanes of other rows hold 0 of this row's sum), before the lanes'
-        // sum -- all in VGPRs (SGPRs are the kernel's scarce registers)
+        // DOT: each lane's part of the row's sum times the row's x (the same
+        // in every lane that holds a part of it), before the lanes' sum
         auto row_out = [&](int ir, double a0, double a1, double a2, double xr0, double xr1, double xr2) {
             if constexpr (DOT) dr += (a0 * xr0 + a1 * xr1) + a2 * xr2;
             wsum3_dpp(a0, a1, a2);
@@ -479,7 +479,10 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
             acc1 += mine ? s1 : 0.0;
             acc2 += mine ? s2 : 0.0;
             if (it.sf & 256) {
-                row_out(irP, acc0, acc1, acc2, c0, c1, c2);
+                // (DOT: P's x in every lane -- in the item P shares with Q the
+                // lanes from s on still hold their parts of P's full passes,
+                // and their c is Q's x)
+                row_out(irP, acc0, acc1, acc2, p0, p1, p2);
                 // (Q's lanes start Q's sum)
                 const bool qs = live && q;
                 acc0 = qs ? s0 : 0.0;

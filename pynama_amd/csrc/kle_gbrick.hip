@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_gsym_brick(const GBrickD
     }
     // the brick's scale: 2^(61 - E), 2^E > (its sums' bound, k_gbrick_bound)
     // x max |x|, as two normal factors (x near the bottom of the exponent
-    // range keeps its 61 bits)
+    // range keeps its 61 bits, sums near the top of it stay below 2^61)
     double S1 = 1.0, S2 = 1.0, T1 = 1.0, T2 = 1.0;
     {
         double m = 0.0, nb = 0.0;
@@ -221,8 +221,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_gsym_brick(const GBrickD
         } else if (m > 0.0) {
             int em;
             (void)frexp(m, &em);
-            const int E = min(max(eb + em, -1070), 1020);
-            const int e1 = min(61 - E, 1000), e2 = 61 - E - e1;
+            const int E = max(eb + em, -1070);  // (<= 2048: no clamp above, or sums near DBL_MAX would pass 2^61)
+            const int e1 = max(min(61 - E, 1000), -1000), e2 = 61 - E - e1;
             S1 = ldexp(1.0, e1);
             S2 = ldexp(1.0, e2);
             T1 = ldexp(1.0, -e1);

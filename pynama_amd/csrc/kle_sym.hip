@@ -394,7 +394,10 @@ __global__ __launch_bounds__(64 * WV, 4) __attribute__((amdgpu_num_sgpr(SYM_XL_S
     __builtin_amdgcn_s_waitcnt(0xC07F);  // LDS stores done (lgkmcnt 0); the value loads stay in flight
     __builtin_amdgcn_s_barrier();
     KLE_PROBE_TS(ts1)
-    double S = 1.0, invS = 1.0;
+    // the scale 2^(61 - E) as two normal factors S S2 (and its inverse), as
+    // the bricks': subnormal x keeps its 61 bits (no flush of sums that fp64
+    // keeps) and E may pass 1023 (sums near DBL_MAX stay below 2^61)
+    double S = 1.0, S2 = 1.0, invS = 1.0, invS2 = 1.0;
     if (DET) {
         // max |x_i| over the tile's rows (every wave computes it; max is exact)
         double m = 0.0;
@@ -416,9 +419,12 @@ __global__ __launch_bounds__(64 * WV, 4) __attribute__((amdgpu_num_sgpr(SYM_XL_S
         } else if (m > 0.0) {
             int em;
             (void)frexp(m, &em);  // 2^em > m
-            const int E = min(max(tile_e[t] + em, -960), 1020);
-            S = ldexp(1.0, 61 - E);
-            invS = ldexp(1.0, E - 61);
+            const int E = max(tile_e[t] + em, -1070);
+            const int e1 = max(min(61 - E, 1000), -1000), e2 = 61 - E - e1;
+            S = ldexp(1.0, e1);
+            S2 = ldexp(1.0, e2);
+            invS = ldexp(1.0, -e1);
+            invS2 = ldexp(1.0, -e2);
         }
     }
     if (any && !(probe & 128)) {  // (timing probe 128: no item loop)
@@ -454,9 +460,9 @@ __global__ __launch_bounds__(64 * WV, 4) __attribute__((amdgpu_num_sgpr(SYM_XL_S
                 if (!live) yd[lane] = t0 + t1 + t2;  // (timing probe: no transposed adds)
             } else if (DET) {
                 unsigned long long *yi = reinterpret_cast<unsigned long long *>(yl);
-                atomicAdd(&yi[rt], fx_of(t0, S));
-                atomicAdd(&yi[RS + rt], fx_of(t1, S));
-                atomicAdd(&yi[2 * RS + rt], fx_of(t2, S));
+                atomicAdd(&yi[rt], fx_of(t0 * S, S2));
+                atomicAdd(&yi[RS + rt], fx_of(t1 * S, S2));
+                atomicAdd(&yi[2 * RS + rt], fx_of(t2 * S, S2));
             } else {
                 atomicAdd(&yl[rt], t0);
                 atomicAdd(&yl[RS + rt], t1);
@@ -505,7 +511,7 @@ __global__ __launch_bounds__(64 * WV, 4) __attribute__((amdgpu_num_sgpr(SYM_XL_S
         const int sl = (rx - g.PX) + SYM_TX * ((ry - g.PY) + TY * rz);
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
-            double v = DET ? fx_to_d(yi[b * RS + kc]) * invS : yl[b * RS + kc];
+            double v = DET ? fx_to_d(yi[b * RS + kc]) * invS * invS2 : yl[b * RS + kc];
             if (own) v += yd[b * TR + sl];
             if (!lat) v = 0.0;
             if (probe & 32)
@@ -914,7 +920,7 @@ __global__ __launch_bounds__(64 * WV) void k_nb_spmv_gsym(
     __syncthreads();
     if (__builtin_amdgcn_readfirstlane(stop) != 0) return;
     KLE_PROBE_TS(ts1)
-    double S = 1.0, invS = 1.0;
+    double S = 1.0, S2 = 1.0, invS = 1.0, invS2 = 1.0;  // (two normal factors each, as the tiles')
     if (DET) {
         // max |x_i| over the group's rows: dictionary positions 0 .. nr-1
         double m = 0.0;
@@ -932,9 +938,12 @@ __global__ __launch_bounds__(64 * WV) void k_nb_spmv_gsym(
         } else if (m > 0.0) {
             int em;
             (void)frexp(m, &em);
-            const int E = min(max(gexp[g] + em, -960), 1020);
-            S = ldexp(1.0, 61 - E);
-            invS = ldexp(1.0, E - 61);
+            const int E = max(gexp[g] + em, -1070);
+            const int e1 = max(min(61 - E, 1000), -1000), e2 = 61 - E - e1;
+            S = ldexp(1.0, e1);
+            S2 = ldexp(1.0, e2);
+            invS = ldexp(1.0, -e1);
+            invS2 = ldexp(1.0, -e2);
         }
     }
     unsigned long long *yi = reinterpret_cast<unsigned long long *>(yl);
@@ -957,9 +966,9 @@ __global__ __launch_bounds__(64 * WV) void k_nb_spmv_gsym(
         if (probe & 1) {
             if (!on) yd[lane] = t0 + t1 + t2;  // (probe 1: no transposed adds)
         } else if (DET) {
-            atomicAdd(&yi[rt], fx_of(t0, S));
-            atomicAdd(&yi[RS + rt], fx_of(t1, S));
-            atomicAdd(&yi[2 * RS + rt], fx_of(t2, S));
+            atomicAdd(&yi[rt], fx_of(t0 * S, S2));
+            atomicAdd(&yi[RS + rt], fx_of(t1 * S, S2));
+            atomicAdd(&yi[2 * RS + rt], fx_of(t2 * S, S2));
         } else {
             atomicAdd(&yl[rt], t0);
             atomicAdd(&yl[RS + rt], t1);
@@ -1004,7 +1013,7 @@ __global__ __launch_bounds__(64 * WV) void k_nb_spmv_gsym(
     for (int t = (probe & 8) ? nw : threadIdx.x; t < nw; t += NT) {  // (probe 8: no partial stores)
         const int tc = min(t, 3 * U - 1);
         const int e = tc / 3, c = tc - 3 * e;
-        double s = DET ? fx_to_d(yi[c * RS + e]) * invS : yl[c * RS + e];
+        double s = DET ? fx_to_d(yi[c * RS + e]) * invS * invS2 : yl[c * RS + e];
         if (e < G) s += yd[tc];
         if (t >= 3 * U) s = 0.0;
         if (probe & 32)
