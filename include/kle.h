@@ -109,7 +109,9 @@ const char *kle_last_error(void);
  * free rows at the far corner of their box -- formed by the gather instead
  * of as items of the bricks; 1 default), "spmv_gather_wps" (the run-mask
  * gather's waves per 64-row slice: 1, 2, 4; 0 default, by the runs per
- * slice), "spmv_gsym_brick" (read at build: graph K on graph bricks, whole
+ * slice), "elem_ghost_rows" (element-wise K, Krhs, Rw on several ranks: the
+ * ghost layer's GEMM over the row groups holding its top-plane rows alone;
+ * 1 default, 0 every row group), "spmv_gsym_brick" (read at build: graph K on graph bricks, whole
  * rounds per CU; 1 default), "ipc_sentinel" (IPC transport debug mode:
  * consumed mailbox slots overwritten with NaN before the ack; 0 default),
  * "ksp_corr_fault" (test hook: correction solves that end in NaN; 0),
@@ -371,7 +373,7 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * three, b = Rw w + Krhs u_bc and K u = b need no assembly at all
  * (MatFS.build(kleType="element"), -kle_mat_type element).
  * kle_mesh_create_box makes every element the same brick, so K u = sum_e
- * S_e^T K_e0 S_e u with K_e0 the first local element's matrix (from the
+ * S_e^T K_e0 S_e u with K_e0 the matrix of global element 0 (from the
  * assembly's own element kernel): one FP64 MFMA GEMM K_e0 x [gathered element
  * vectors] and a gather per node in ascending element order -- bitwise
  * repeatable, and equal to the assembled product to rounding plus the spread
@@ -384,14 +386,26 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * getters, kle_mat_get_info (nz_used = 0: no entry is stored),
  * kle_mat_spmv_bytes, kle_mat_spmv_kernel, kle_mat_destroy and
  * kle_ksp_set_operators with cg (classic and single reduction: the generic
- * paths) or gmres and PC none or jacobi.  Calls that need stored
- * values return KLE_ERR_SUP: set_values, assemble, axpy, diagonal_scale,
- * get_row, get_csr, get_csr_size, convert_aij, duplicate, set_symmetric,
- * move_values, time_local_spmv, PC lu.  Rw also refuses kle_mat_get_diagonal
+ * paths), pipecg or gmres and PC none or jacobi, and
+ * kle_mat_time_local_spmv (this rank's element launches and its gather, no
+ * halo).  Calls that need stored values return KLE_ERR_SUP: set_values,
+ * assemble, axpy, diagonal_scale, get_row, get_csr, get_csr_size,
+ * convert_aij, duplicate, set_symmetric, move_values, PC lu.  Rw also refuses
+ * kle_mat_get_diagonal
  * (KLE_ERR_SUP), and kle_ksp_set_operators refuses a non-square operator
  * (the 2-D Rw) before anything is launched.
- * Needs a box mesh with its Dirichlet set, 2-D or 3-D, on one rank;
- * KLE_ERR_SUP for unstructured meshes, no-slip meshes and nranks > 1. */
+ * Several ranks (the mesh's slab partition must be the context's): owner
+ * computes.  The tables hold ext-local node ids over every element touching
+ * an owned node (one ghost layer below, the own layers, of which the top one
+ * reads the upper ghost plane); x is a ghosted mesh vector (kle_vec_create_mesh)
+ * read through its allocation after one forward halo, which with halo overlap
+ * on (kle_mat_set_halo_overlap, the default) runs on the comm stream beside
+ * the interior elements; the gather, the Dirichlet flags, kle_mat_get_diagonal
+ * and kle_mat_copy_dirichlet_rows cover the owned rows, which are the one-rank
+ * product's bit for bit.  The 32-bit table limits apply to the local sizes.
+ * Needs a box mesh with its Dirichlet set, 2-D or 3-D; KLE_ERR_SUP for
+ * unstructured meshes, no-slip meshes and a mesh whose nranks is not the
+ * context's. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Element-wise collocation operator of a uniform box mesh: which 0 Curl
  * [dim_w N x dim N], 1 SrT [dim_s N x dim N], 2 DivSrT [dim N x dim_s N], the
@@ -405,7 +419,7 @@ int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **o
  * (k_colloc_gather).  No atomics: bitwise repeatable, and equal to the
  * assembled product to rounding plus the spread of the element geometry over
  * the mesh.  c_l, inv J and the derivative table come from the assembly's own
- * geometry path on the first element's corners.  At creation the dense M_e0 of
+ * geometry path on the corners of global element 0.  At creation the dense M_e0 of
  * the factored tables is compared on the host with the element matrix of the
  * assembly path (kle_element_ops): exactly 0 off the grid lines, a few ulps on
  * them, KLE_ERR_STATE otherwise.
@@ -417,10 +431,15 @@ int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **o
  * kle_mat_get_info (nz_used = 0), kle_mat_spmv_bytes, kle_mat_spmv_kernel and
  * kle_mat_destroy.  KLE_ERR_SUP: everything the element-wise Rw refuses, and
  * kle_mat_get_diagonal, kle_ksp_set_operators, kle_mat_copy_dirichlet_rows.
- * Needs a box mesh on one rank, ngl 2..8; no Dirichlet set is needed and
- * no-slip box meshes are accepted (the operators carry no boundary rule).
- * KLE_ERR_SUP for unstructured meshes and nranks > 1, KLE_ERR_ARG for a bad
- * which. */
+ * kle_mat_time_local_spmv works as for the element-wise K.
+ * Several ranks: as kle_mat_create_kle_element -- ext-local tables over every
+ * element touching an owned node, one forward halo of the ghosted x beside
+ * the interior elements, owned rows bit-identical to the one-rank product; a
+ * workgroup takes whole elements, so the ghost layer is computed whole.
+ * Needs a box mesh, ngl 2..8; no Dirichlet set is needed and no-slip box
+ * meshes are accepted (the operators carry no boundary rule).  KLE_ERR_SUP
+ * for unstructured meshes and a mesh whose nranks is not the context's,
+ * KLE_ERR_ARG for a bad which. */
 int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Dense collocation element matrices of local element e as the assembly forms
  * them, before the nodal weight (parity tests, the creation check above):
@@ -552,7 +571,9 @@ int kle_mat_spmv_kernel(const kle_mat *A, char *buf, int buflen);
  * and the gather of every row they touch, with no halo exchange either way
  * (the ghost x as they are).  A part's own kernel time, free of its
  * neighbours -- ranks that share a GPU take turns.  Box-brick symmetric
- * storage only (KLE_ERR_ARG otherwise); y's ghost-row sums are not sent. */
+ * storage (y's ghost-row sums are not sent) or an element-wise operator (its
+ * element launches over this rank's local elements and the owned-row gather,
+ * at any rank count); KLE_ERR_ARG otherwise. */
 int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, double *ms);
 
 /* -------------------------------------------------------------------- ksp */

@@ -27,6 +27,17 @@
 // No atomics, fixed order: the product is repeatable bit for bit.  Both
 // kernels do nothing once the Krylov reason word is set.  The operators carry
 // no boundary rule, so no Dirichlet or no-slip table is read.
+//
+// Several ranks (slabs of whole element layers): as the element-wise K
+// (kle_elem.hip) -- the connectivity in ext-local node ids over every element
+// touching an owned node, x read through the vector's ghosted allocation after
+// one forward halo, winv and the incidence lists for the owned nodes, whose
+// incident elements are all local, the element kernel launched over element
+// ranges (elem_ranges: the interior beside the halo, the ghost layer and the
+// top layer after it).  A workgroup takes whole elements, so the ghost layer
+// is computed whole although only its top plane is gathered.  geo is that of
+// global element 0 on every rank: the owned rows are the one-rank product's
+// bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -42,13 +53,13 @@ constexpr int CL_SC2 = 448;  // 2-D: 64 ngl 2 elements, strides 3 / 7
 struct CollocOp {
     int which = 0, dim = 3, cw = 3, rw = 3, ngl = 0, nn = 0, maxinc = 8;
     int neb = 1, sy = 0, sz = 0, se = 0;  // elements per workgroup; LDS line, plane and element strides
-    int64_t E = 0, N = 0;
+    int64_t E = 0, N = 0;       // local elements, owned nodes
     double *d_dh = nullptr;     // [ngl][ngl] 1-D derivative table
     double *d_geo = nullptr;    // [nn][1 + dim^2] c_l, inv J of the first element
-    double *d_winv = nullptr;   // [N] 1 / lumped nodal weight
+    double *d_winv = nullptr;   // [N] 1 / lumped nodal weight of the owned nodes
     double *d_ws = nullptr;     // [E][nn][rw] element results
-    int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order
-    int32_t *d_inc = nullptr;   // [N][maxinc] node -> e * nn + l, ascending e, -1 padded
+    int32_t *d_conn = nullptr;  // [E][nn] element -> ext-local node, tensor order
+    int32_t *d_inc = nullptr;   // [N][maxinc] owned node -> e * nn + l, ascending e, -1 padded
 };
 
 // OP 0 Curl [dim_w x dim], 1 SrT [dim_s x dim], 2 DivSrT [dim x dim_s]
@@ -88,7 +99,8 @@ __host__ __device__ constexpr double colloc_coef(int a, int b, int d)
 }
 
 template <int DIM, int OP>
-__global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
+__global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t eb,
+                                                     int64_t E,
                                                      const double *__restrict__ dh, const double *__restrict__ geo,
                                                      const int32_t *__restrict__ conn, const double *__restrict__ x,
                                                      double *__restrict__ ws, const int *__restrict__ istate)
@@ -99,7 +111,7 @@ __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, i
     __shared__ double sx[CW * SC];
     __shared__ double sd[8 * CL_SD];
     const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * neb;
+    const int64_t e0 = eb + (int64_t)blockIdx.x * neb;  // elements [eb, E) of the launch's range
     const int nt = (int)min((int64_t)neb, E - e0) * nn;  // (element, node) pairs of this batch
     const int64_t t0 = e0 * nn;
     if (tid < ngl * ngl) sd[(tid / ngl) * CL_SD + tid % ngl] = dh[tid];
@@ -197,35 +209,44 @@ __global__ __launch_bounds__(256) void k_colloc_gather(int64_t N, int maxinc, co
     for (int a = 0; a < RW; ++a) y[node * RW + a] = s[a] * wi;
 }
 
+// the element kernel over elements [e0, e1) (x: the ghosted allocation), or with e0 < 0 the gather
 template <int DIM, int OP>
-static void launch_colloc(const CollocOp *P, hipStream_t st, const double *x, double *y, const int *istate)
+static void launch_colloc(const CollocOp *P, hipStream_t st, int64_t e0, int64_t e1, const double *x, double *y,
+                          const int *istate)
 {
-    const unsigned ge = (unsigned)((P->E + P->neb - 1) / P->neb), gn = (unsigned)((P->N + 255) / 256);
-    hipLaunchKernelGGL((k_colloc_elem<DIM, OP>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se,
-                       P->E, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate);
+    if (e0 >= 0) {
+        const unsigned ge = (unsigned)((e1 - e0 + P->neb - 1) / P->neb);
+        hipLaunchKernelGGL((k_colloc_elem<DIM, OP>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz,
+                           P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate);
+        return;
+    }
+    const unsigned gn = (unsigned)((P->N + 255) / 256);
     hipLaunchKernelGGL((k_colloc_gather<colloc_rw(DIM, OP)>), dim3(gn), dim3(256), 0, st, P->N, P->maxinc, P->d_inc,
                        P->d_winv, P->d_ws, y, istate);
 }
 
-int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
+int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local)
 {
     const CollocOp *P = A->colloc;
     if (!P) return fail(KLE_ERR_STATE, "collocation operator without tables");
-    if (x->n_local != A->n_local || y->n_local != A->m_local || x->ghost_lo || x->ghost_hi)
-        return fail(KLE_ERR_SIZ, "collocation operator: vector layout does not match");
-    if (x->d == y->d) return fail(KLE_ERR_ARG, "collocation operator: y must not alias x");
+    KLE_TRY(elem_check_vecs(A, x, y, "collocation operator"));
     hipStream_t st = A->ctx->stream;
-    switch (P->dim * 3 + P->which) {
-    case 6: launch_colloc<2, 0>(P, st, x->d, y->d, istate); break;
-    case 7: launch_colloc<2, 1>(P, st, x->d, y->d, istate); break;
-    case 8: launch_colloc<2, 2>(P, st, x->d, y->d, istate); break;
-    case 9: launch_colloc<3, 0>(P, st, x->d, y->d, istate); break;
-    case 10: launch_colloc<3, 1>(P, st, x->d, y->d, istate); break;
-    case 11: launch_colloc<3, 2>(P, st, x->d, y->d, istate); break;
-    default: return fail(KLE_ERR_STATE, "collocation operator: bad tables");
-    }
-    KLE_HIP(hipGetLastError());
-    return 0;
+    auto launch = [&](int64_t e0, int64_t e1) -> int {
+        switch (P->dim * 3 + P->which) {
+        case 6: launch_colloc<2, 0>(P, st, e0, e1, x->base, y->d, istate); break;
+        case 7: launch_colloc<2, 1>(P, st, e0, e1, x->base, y->d, istate); break;
+        case 8: launch_colloc<2, 2>(P, st, e0, e1, x->base, y->d, istate); break;
+        case 9: launch_colloc<3, 0>(P, st, e0, e1, x->base, y->d, istate); break;
+        case 10: launch_colloc<3, 1>(P, st, e0, e1, x->base, y->d, istate); break;
+        case 11: launch_colloc<3, 2>(P, st, e0, e1, x->base, y->d, istate); break;
+        default: return fail(KLE_ERR_STATE, "collocation operator: bad tables");
+        }
+        KLE_HIP(hipGetLastError());
+        return 0;
+    };
+    // (the ghost layer whole: a workgroup takes whole elements)
+    KLE_TRY(elem_ranges(A, x, local, [&](int64_t e0, int64_t e1, bool) -> int { return launch(e0, e1); }));
+    return launch(-1, -1);
 }
 
 void colloc_drop(kle_mat *A)
@@ -250,7 +271,7 @@ double colloc_spmv_bytes(const kle_mat *A)
 {
     const CollocOp *P = A->colloc;
     if (!P) return 0.0;
-    return 4.0 * P->E * P->nn + 8.0 * A->n_local + 8.0 * P->ngl * P->ngl + 8.0 * P->nn * (1 + P->dim * P->dim) +
+    return 4.0 * P->E * P->nn + 8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * P->ngl * P->ngl + 8.0 * P->nn * (1 + P->dim * P->dim) +
            2.0 * 8.0 * P->E * P->nn * P->rw + 4.0 * P->N * P->maxinc + 8.0 * P->N + 8.0 * A->m_local;
 }
 
@@ -335,31 +356,16 @@ extern "C" int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int wh
     KLE_ARG(which >= 0 && which <= 2, "which must be 0 (Curl), 1 (SrT) or 2 (DivSrT)");
     if (m->kind != 0)
         return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
-    if (m->nranks > 1 || ctx->nranks > 1)
-        return fail(KLE_ERR_SUP, "element-wise operator: one rank only (%d ranks)", std::max(m->nranks, ctx->nranks));
     const int dim = m->dim, ngl = m->ngl, nn = m->nn(), maxinc = 1 << dim, G1 = 1 + dim * dim;
     KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "element-wise operator: dim 2 or 3, ngl 2..8");
     const int rw = colloc_rw(dim, which), cw = colloc_cw(dim, which);
-    const int64_t E = m->elem_end - m->elem_begin, N = m->node_end - m->node_begin;
-    KLE_ARG(E >= 1 && N >= 1 && m->ext_begin == 0 && m->node_begin == 0 && m->ext_end == N, "unexpected one-rank layout");
-    if (E * nn >= INT32_MAX || N * std::max(rw, cw) >= INT32_MAX)
-        return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
+    ElemLayout L;
+    KLE_TRY(elem_layout(ctx, m, std::max(rw, cw), &L));
+    const int64_t E = L.E, N = L.N;
 
-    // tables (host), validated before upload
-    std::vector<int64_t> conn64((size_t)E * nn);
-    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
-    std::vector<int32_t> conn((size_t)E * nn), inc((size_t)N * maxinc, -1);
-    std::vector<uint8_t> cnt((size_t)N, 0);
-    for (int64_t k = 0; k < E * nn; ++k) {
-        const int64_t g = conn64[k];
-        if (g < 0 || g >= N)
-            return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld outside the mesh", (long long)k);
-        conn[k] = (int32_t)g;
-        if (cnt[g] >= maxinc)
-            return fail(KLE_ERR_OUTOFRANGE, "element operator: node %lld lies in more than %d elements", (long long)g, maxinc);
-        inc[g * maxinc + cnt[g]++] = (int32_t)k;  // k = e * nn + l, ascending e
-    }
-    KLE_TRY(elem_validate(conn, inc, N, E, nn, maxinc));
+    // tables (host) in ext-local node ids, validated before upload
+    std::vector<int32_t> conn, inc;
+    KLE_TRY(elem_tables(m, L, conn, inc));
 
     // LDS layout: odd strides (in doubles) of the y lines, z planes and elements
     // (a workgroup's only element needs no element stride)
@@ -369,10 +375,12 @@ extern "C" int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int wh
         return fail(KLE_ERR_STATE, "collocation operator: %d elements of stride %d exceed the LDS tile", neb, se);
 
     KLE_HIP(hipSetDevice(ctx->device));
-    // c_l, inv J and D through the assembly's own geometry path on the first
-    // element's corners, and the element matrix it forms there
+    // c_l, inv J and D through the assembly's own geometry path on the corners
+    // of global element 0, and the element matrix it forms there
+    kle_mesh m0;
+    first_element_mesh(m, &m0);
     std::vector<double> geo, dh, dense;
-    KLE_TRY(element_ops(ctx, m, 0, geo, dh, which == 0 ? &dense : nullptr, which == 1 ? &dense : nullptr,
+    KLE_TRY(element_ops(ctx, &m0, 0, geo, dh, which == 0 ? &dense : nullptr, which == 1 ? &dense : nullptr,
                         which == 2 ? &dense : nullptr));
     if ((int)geo.size() != nn * G1 || (int)dh.size() != ngl * ngl)
         return fail(KLE_ERR_STATE, "collocation operator: geometry tables do not match the element");
@@ -405,13 +413,8 @@ extern "C" int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int wh
     kle_mat *A = new kle_mat;
     CollocOp *P = new CollocOp;
     A->ctx = ctx;
-    A->kind = 2;
     A->colloc = P;
-    A->R = rw;
-    A->C = cw;
-    A->nrows = N;
-    A->m_global = A->m_local = N * rw;
-    A->n_global = A->n_local = N * cw;
+    elem_mat_fields(A, m, L, rw, cw);
     P->which = which;
     P->dim = dim;
     P->cw = cw;

@@ -779,6 +779,9 @@ int kle_set_tuning(const char *key, int value)
     } else if (k == "spmv_brick_singles") {
         KLE_ARG(value == 0 || value == 1, "spmv_brick_singles: 0 or 1");
         g_tune.spmv_brick_singles = value;
+    } else if (k == "elem_ghost_rows") {
+        KLE_ARG(value == 0 || value == 1, "elem_ghost_rows: 0 or 1");
+        g_tune.elem_ghost_rows = value;
                         } else if (k == "spmv_gather_wps") {
         KLE_ARG(value == 0 || value == 1 || value == 2 || value == 4, "spmv_gather_wps: 0 (auto), 1, 2 or 4");
         g_tune.spmv_gather_wps = value;
@@ -888,6 +891,7 @@ int kle_get_tuning(const char *key, int *value)
     else if (k == "spmv_brick_split") *value = g_tune.spmv_brick_split;
     else if (k == "spmv_brick_singles") *value = g_tune.spmv_brick_singles;
     else if (k == "spmv_brick_pair") *value = g_tune.spmv_brick_pair;
+    else if (k == "elem_ghost_rows") *value = g_tune.elem_ghost_rows;
     else if (k == "spmv_gather_wps") *value = g_tune.spmv_gather_wps;
     else if (k == "spmv_gsym_brick") *value = g_tune.spmv_gsym_brick;
     else if (k == "upd_unroll") *value = g_tune.upd_unroll;

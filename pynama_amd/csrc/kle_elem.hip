@@ -39,6 +39,20 @@
 //                  element) order -- fixed order, no atomics, bitwise
 //                  repeatable.  Dirichlet rows: y_i = x_i (K, Krhs); 0 for Rw,
 //                  which reads neither x nor the element results there.
+//
+// Several ranks (slabs of whole element layers, kle_mesh_create_box): owner
+// computes.  A rank's local elements are every element touching an owned node
+// -- one ghost layer below (rank > 0), its own layers, the top one of which
+// reads the single upper ghost plane -- so the tables hold ext-local node ids
+// (global id - ext_begin), x is read through the vector's ghosted allocation
+// after one forward halo, and the gather runs over the owned nodes alone.  The
+// GEMM is launched over element ranges (elem_ranges): the interior elements
+// beside the halo, the ghost layer and the top layer after it.  Of a ghost-
+// layer element only the top-plane rows [nd - nd / ngl, nd) are ever gathered:
+// its launch covers the row groups holding them and no other.  K_e0 is that of
+// global element 0 on every rank and neither the per-element accumulation nor
+// the ascending-element gather depends on the partition, so a rank's owned
+// rows are the one-rank product's bit for bit.
 #include <algorithm>
 #include <cstring>
 
@@ -48,13 +62,14 @@ namespace kle {
 
 struct ElemOp {
     int which = 0, dim = 3, cw = 3, nn = 0, nd = 0, ndp = 0, nc = 0, ncp = 0, maxinc = 8, nct = 1;
-    int64_t E = 0, N = 0;
+    int64_t E = 0, N = 0;       // local elements, owned nodes
+    int rg_top = 0;             // first 128-row group holding a top-plane row (the ghost layer's launch starts there)
     double *d_kt = nullptr;     // K_e0 (Rw_e0) padded to ndp x ncp in MFMA operand order [row tile][k step][lane]
     double *d_kdiag = nullptr;  // [nd] its diagonal (K, Krhs)
     double *d_ws = nullptr;     // [E][nd] element results
-    int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order; -1 where the operator drops the entry
-    int32_t *d_inc = nullptr;   // [N][maxinc] node -> e * nn + l, ascending e, -1 padded
-    uint8_t *d_dir = nullptr;   // [N] Dirichlet flag
+    int32_t *d_conn = nullptr;  // [E][nn] element -> ext-local node, tensor order; -1 where the operator drops the entry
+    int32_t *d_inc = nullptr;   // [N][maxinc] owned node -> e * nn + l, ascending e, -1 padded
+    uint8_t *d_dir = nullptr;   // [N] Dirichlet flag of the owned nodes
 };
 
 constexpr int EG_KC = 64;            // k rows of X per LDS chunk
@@ -64,8 +79,8 @@ constexpr int EG_ROWS = 4 * EG_TR * 16;  // rows per workgroup
 typedef double edbl4 __attribute__((ext_vector_type(4)));
 
 template <int CW, int NCT>
-__global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int nc, int ncp, int64_t E,
-                                                      const double *__restrict__ kt,
+__global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int nc, int ncp, int64_t eb,
+                                                      int64_t E, int rg0, const double *__restrict__ kt,
                                                       const int32_t *__restrict__ mconn,
                                                       const double *__restrict__ x, double *__restrict__ ws,
                                                       const int *__restrict__ istate)
@@ -77,8 +92,8 @@ __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd
     __shared__ double sX[EG_KC * SX];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
-    const int64_t e0 = (int64_t)blockIdx.x * NE;
-    const int rt0 = ((int)blockIdx.y * 4 + wv) * EG_TR;  // this wave's first row tile
+    const int64_t e0 = eb + (int64_t)blockIdx.x * NE;              // elements [eb, E) of the launch's range
+    const int rt0 = ((rg0 + (int)blockIdx.y) * 4 + wv) * EG_TR;  // this wave's first row tile (row groups from rg0)
     const int ntile = ndp >> 4, nks = ncp >> 2;
 
     const edbl4 z4 = {0.0, 0.0, 0.0, 0.0};
@@ -230,15 +245,28 @@ __global__ __launch_bounds__(256) void k_elem_copy_dirichlet(int64_t n, int dim,
 
 // Every index the device tables hold, checked on the host before upload: a
 // bad table is an error code, never an out-of-range access.
-int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E, int nn,
+// conn holds ext-local node ids in [0, next); inc covers the owned nodes, ext
+// nodes [own0, own0 + N).  Elements [eghost, eint1) (run beside the halo) may
+// name owned nodes only, and an element below eghost (the ghost layer) may be
+// gathered only at its top-plane nodes l >= ltop.
+int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, const ElemLayout &L, int nn,
                   int maxinc)
 {
+    const int64_t N = L.N, E = L.E;
+    if (E < 1 || N < 1 || L.own0 < 0 || L.own0 + N > L.next || L.eghost < 0 || L.eghost > L.eint1 || L.eint1 > E ||
+        L.ltop < 0 || L.ltop > nn)
+        return fail(KLE_ERR_OUTOFRANGE, "element operator: inconsistent element ranges");
     if ((int64_t)conn.size() != E * nn || (int64_t)inc.size() != N * maxinc)
         return fail(KLE_ERR_SIZ, "element operator: table sizes do not match the mesh");
-    for (int64_t k = 0; k < E * nn; ++k)
-        if (conn[k] < 0 || conn[k] >= N)
+    for (int64_t k = 0; k < E * nn; ++k) {
+        if (conn[k] < 0 || conn[k] >= L.next)
             return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld = %d outside [0, %lld)",
-                        (long long)k, conn[k], (long long)N);
+                        (long long)k, conn[k], (long long)L.next);
+        const int64_t e = k / nn;
+        if (e >= L.eghost && e < L.eint1 && (conn[k] < L.own0 || conn[k] >= L.own0 + N))
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: interior element %lld names the ghost node %d",
+                        (long long)e, conn[k]);
+    }
     for (int64_t i = 0; i < N; ++i) {
         bool ended = false;
         int32_t prev = -1;
@@ -250,7 +278,8 @@ int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &
                 ended = true;
                 continue;
             }
-            if (ended || (int64_t)t >= E * nn || conn[t] != i || (prev >= 0 && t / nn <= prev / nn))
+            if (ended || (int64_t)t >= E * nn || conn[t] != i + L.own0 || (prev >= 0 && t / nn <= prev / nn) ||
+                (t / nn < L.eghost && t % nn < L.ltop))
                 return fail(KLE_ERR_OUTOFRANGE, "element operator: incidence entry %d of node %lld is inconsistent", j,
                             (long long)i);
             prev = t;
@@ -259,31 +288,78 @@ int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &
     return 0;
 }
 
+// elements [e0, e1), row groups from rg0 on
 template <int CW>
-static void launch_gemm(const ElemOp *P, dim3 grid, hipStream_t st, const double *x, const int *istate)
+static void launch_gemm(const ElemOp *P, int64_t e0, int64_t e1, int rg0, hipStream_t st, const double *x,
+                        const int *istate)
 {
+    const int ne = 16 * P->nct;
+    dim3 grid((unsigned)((e1 - e0 + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS - rg0));
 #define KLE_ELEM_GEMM(NCT)                                                                                      \
     hipLaunchKernelGGL((k_elem_gemm<CW, NCT>), grid, dim3(256), 0, st, P->which == 1, P->nn, P->nd, P->ndp, P->nc, \
-                       P->ncp, P->E, P->d_kt, P->d_conn, x, P->d_ws, istate)
+                       P->ncp, e0, e1, rg0, P->d_kt, P->d_conn, x, P->d_ws, istate)
     if (P->nct == 2) KLE_ELEM_GEMM(2);
     else KLE_ELEM_GEMM(1);
 #undef KLE_ELEM_GEMM
 }
 
-int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
+// The element launches of one product of an element-wise operator (kind 2),
+// launch(e0, e1, ghost layer?) per element range.  One rank or local (timing:
+// no halo): every element at once.  Several ranks: one forward halo of x; with
+// overlap the interior elements run on the compute stream beside the halo on
+// the comm stream, the ghost layer and the top layer after it -- as the
+// node-block product's interior and ghost-dependent rows (kle_mat.hip spmv).
+int elem_ranges(kle_mat *A, const kle_vec *x, bool local, const std::function<int(int64_t, int64_t, bool)> &launch)
+{
+    kle_ctx *c = A->ctx;
+    // [0, g1) the ghost layer, [g1, i1) the interior, [i1, E) the top layer
+    const int64_t E = A->el_n, g1 = A->el_ghost, i1 = A->el_int1;
+    if (E < 1 || g1 < 0 || g1 > i1 || i1 > E) return fail(KLE_ERR_STATE, "element operator: bad element ranges");
+    const bool overlap = c->nranks > 1 && !local && spmv_uses_comm_stream(A, x);
+    if (!overlap) {
+        if (c->nranks > 1 && !local)
+            KLE_TRY(halo_exchange(c, x->base, x->ghost_lo, x->n_local, x->ghost_hi, x->lo_rank, x->hi_rank,
+                                  x->send_lo, x->send_hi, nullptr, x->plan.get()));
+        if (g1 > 0) KLE_TRY(launch(0, g1, true));
+        return g1 < E ? launch(g1, E, false) : 0;
+    }
+    SideBusy busy(c);
+    KLE_HIP(hipEventRecord(c->ev_x_ready, c->stream));
+    KLE_HIP(hipStreamWaitEvent(c->comm_stream, c->ev_x_ready, 0));
+    KLE_TRY(launch(g1, i1, false));  // (overlap only where g1 < i1: spmv_uses_comm_stream)
+    KLE_TRY(halo_exchange(c, x->base, x->ghost_lo, x->n_local, x->ghost_hi, x->lo_rank, x->hi_rank, x->send_lo,
+                          x->send_hi, c->comm_stream, x->plan.get()));
+    KLE_HIP(hipEventRecord(c->ev_halo_done, c->comm_stream));
+    KLE_HIP(hipStreamWaitEvent(c->stream, c->ev_halo_done, 0));
+    if (g1 > 0) KLE_TRY(launch(0, g1, true));
+    return i1 < E ? launch(i1, E, false) : 0;
+}
+
+// x and y of a product against the operator's layout: x a ghosted vector of
+// the column space (read through its allocation in ext indices), y the owned rows
+int elem_check_vecs(const kle_mat *A, const kle_vec *x, const kle_vec *y, const char *what)
+{
+    if (x->n_local != A->n_local || y->n_local != A->m_local || x->ghost_lo != A->ghost_lo ||
+        x->ghost_hi != A->ghost_hi || !x->base || x->d != x->base + x->ghost_lo)
+        return fail(KLE_ERR_SIZ, "%s: vector layout does not match", what);
+    if (x->d == y->d) return fail(KLE_ERR_ARG, "%s: y must not alias x", what);
+    return 0;
+}
+
+int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local)
 {
     const ElemOp *P = A->elem;
     if (!P) return fail(KLE_ERR_STATE, "element operator without tables");
-    if (x->n_local != A->n_local || y->n_local != A->m_local || x->ghost_lo || x->ghost_hi)
-        return fail(KLE_ERR_SIZ, "element operator: vector layout does not match");
-    if (x->d == y->d) return fail(KLE_ERR_ARG, "element operator: y must not alias x");
+    KLE_TRY(elem_check_vecs(A, x, y, "element operator"));
     hipStream_t st = A->ctx->stream;
-    const int ne = 16 * P->nct;
-    dim3 grid((unsigned)((P->E + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS));
-    if (P->cw == 1) launch_gemm<1>(P, grid, st, x->d, istate);
-    else if (P->cw == 2) launch_gemm<2>(P, grid, st, x->d, istate);
-    else launch_gemm<3>(P, grid, st, x->d, istate);
-    KLE_HIP(hipGetLastError());
+    KLE_TRY(elem_ranges(A, x, local, [&](int64_t e0, int64_t e1, bool ghost) -> int {
+        const int rg0 = ghost && g_tune.elem_ghost_rows ? P->rg_top : 0;
+        if (P->cw == 1) launch_gemm<1>(P, e0, e1, rg0, st, x->base, istate);
+        else if (P->cw == 2) launch_gemm<2>(P, e0, e1, rg0, st, x->base, istate);
+        else launch_gemm<3>(P, e0, e1, rg0, st, x->base, istate);
+        KLE_HIP(hipGetLastError());
+        return 0;
+    }));
     const int64_t n = P->N * P->dim;
     dim3 gg((unsigned)((n + 255) / 256));
     const double *xd = P->which == 2 ? nullptr : x->d;  // Rw: no Dirichlet diagonal, x is never read by the gather
@@ -337,7 +413,7 @@ double elem_spmv_bytes(const kle_mat *A)
     const ElemOp *P = A->elem;
     if (!P) return 0.0;
     return 8.0 * P->nd * P->nc + 4.0 * P->E * P->nn + 4.0 * P->N * P->maxinc + 1.0 * P->N +
-           8.0 * A->n_local + 8.0 * A->m_local + 2.0 * 8.0 * P->E * P->nd;
+           8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * A->m_local + 2.0 * 8.0 * P->E * P->nd;
 }
 
 std::string elem_kernel_name(const kle_mat *A)
@@ -346,6 +422,114 @@ std::string elem_kernel_name(const kle_mat *A)
     if (!P) return "?";
     return "k_elem_gemm<" + std::to_string(P->cw) + "," + std::to_string(P->nct) + ">+k_elem_gather<" +
            std::to_string(P->dim) + ">";
+}
+
+// The part of a box mesh an element-wise operator on ctx works on.  The mesh's
+// partition must be the context's (a one-rank context takes no part of a
+// several-rank mesh); the 32-bit tables bound the local sizes, bw the widest
+// block of the operator.
+int elem_layout(const kle_ctx *ctx, const kle_mesh *m, int bw, ElemLayout *out)
+{
+    if (m->kind != 0)
+        return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
+    if (m->nranks != ctx->nranks)
+        return fail(KLE_ERR_SUP, "element-wise operator: the mesh is partitioned for %d ranks, the context has %d",
+                    m->nranks, ctx->nranks);
+    KLE_ARG(m->rank == ctx->rank, "mesh partition does not match ctx");
+    ElemLayout L;
+    L.N = m->node_end - m->node_begin;
+    L.next = m->ext_end - m->ext_begin;
+    L.own0 = m->node_begin - m->ext_begin;
+    L.E = m->elem_end - m->elem_begin;
+    L.eghost = m->rank > 0 ? m->elem_layer : 0;
+    L.eint1 = m->rank < m->nranks - 1 ? L.E - m->elem_layer : L.E;
+    L.ltop = m->nn() - m->nn() / m->ngl;
+    KLE_ARG(L.E >= 1 && L.N >= 1 && L.own0 >= 0 && L.own0 + L.N <= L.next && L.eghost <= L.eint1 &&
+                (m->nranks > 1 || (L.own0 == 0 && L.next == L.N && m->node_begin == 0)),
+            "unexpected slab layout");
+    if (L.E * m->nn() >= INT32_MAX || L.next * bw >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
+    *out = L;
+    return 0;
+}
+
+// conn [E][nn] in ext-local node ids and the owned nodes' incidence lists
+// inc [N][maxinc] (e * nn + l, ascending e, -1 padded), validated
+int elem_tables(const kle_mesh *m, const ElemLayout &L, std::vector<int32_t> &conn, std::vector<int32_t> &inc)
+{
+    const int nn = m->nn(), maxinc = 1 << m->dim;
+    std::vector<int64_t> conn64((size_t)L.E * nn);
+    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
+    conn.assign((size_t)L.E * nn, 0);
+    inc.assign((size_t)L.N * maxinc, -1);
+    std::vector<uint8_t> cnt((size_t)L.N, 0);
+    for (int64_t k = 0; k < L.E * nn; ++k) {
+        const int64_t g = conn64[k] - m->ext_begin;
+        if (g < 0 || g >= L.next)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld outside the mesh", (long long)k);
+        conn[k] = (int32_t)g;
+        const int64_t o = g - L.own0;
+        if (o < 0 || o >= L.N) continue;  // a ghost node: read, never written
+        if (cnt[o] >= maxinc)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: node %lld lies in more than %d elements",
+                        (long long)conn64[k], maxinc);
+        inc[o * maxinc + cnt[o]++] = (int32_t)k;  // k = e * nn + l, ascending e
+    }
+    return elem_validate(conn, inc, L, nn, maxinc);
+}
+
+// sizes, ownership and the column space's halo plan, as kle_assemble_kle sets
+// them for a node-block matrix of R x C blocks on the same mesh
+void elem_mat_fields(kle_mat *A, const kle_mesh *m, const ElemLayout &L, int R, int C)
+{
+    A->kind = 2;
+    A->R = R;
+    A->C = C;
+    A->nrows = L.N;
+    A->m_local = L.N * R;
+    A->n_local = L.N * C;
+    A->m_global = m->N * R;
+    A->n_global = m->N * C;
+    A->row_lo = m->node_begin * R;
+    A->col_lo = m->node_begin * C;
+    A->node_begin = m->node_begin;
+    A->ext_begin = m->ext_begin;
+    A->ext_nodes = L.next;
+    A->lo_rank = m->halo_lo_rank;
+    A->hi_rank = m->halo_hi_rank;
+    A->ghost_lo = L.own0 * C;
+    A->ghost_hi = (L.next - L.own0 - L.N) * C;
+    A->send_lo = m->send_lo_nodes * C;
+    A->send_hi = m->send_hi_nodes * C;
+    A->el_n = L.E;
+    A->el_ghost = L.eghost;
+    A->el_int1 = L.eint1;
+    if (const char *e = getenv("KLE_HALO_OVERLAP")) A->halo_overlap = atoi(e) != 0;
+}
+
+// A one-element, one-rank mesh holding global element 0 of m: every rank
+// forms K_e0 and the operator geometry from the same corners, so the tables
+// are the same bits whatever the partition.
+void first_element_mesh(const kle_mesh *m, kle_mesh *o)
+{
+    o->dim = m->dim;
+    o->ngl = m->ngl;
+    o->p = m->p;
+    for (int d = 0; d < 3; ++d) {
+        o->nel[d] = m->nel[d];
+        o->L[d] = m->L[d];
+        o->lower[d] = m->lower[d];
+        o->upper[d] = m->upper[d];
+        o->h[d] = m->h[d];
+    }
+    o->N = m->N;
+    o->E = m->E;
+    o->xi = m->xi;
+    o->axis = m->axis;
+    o->plane = m->plane;
+    o->elem_layer = m->elem_layer;
+    o->elem_begin = 0;
+    o->elem_end = 1;
 }
 
 }  // namespace kle
@@ -374,43 +558,33 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     KLE_ARG(which >= 0 && which <= 2, "which must be 0 (K), 1 (Krhs) or 2 (Rw)");
     if (m->kind != 0) return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
     if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "element-wise operator: no-slip meshes are not supported");
-    if (m->nranks > 1 || ctx->nranks > 1)
-        return fail(KLE_ERR_SUP, "element-wise operator: one rank only (%d ranks)", std::max(m->nranks, ctx->nranks));
-    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
     // rows nd = dim nn (padded to the row tile); columns nc = cw nn (padded to the k step)
     const int dim = m->dim, nn = m->nn(), nd = dim * nn, ndp = (nd + 15) & ~15, maxinc = 1 << dim;
     const int cw = which == 2 ? (dim == 2 ? 1 : 3) : dim, nc = cw * nn, ncp = (nc + 3) & ~3;
-    const int64_t E = m->elem_end - m->elem_begin, N = m->node_end - m->node_begin;
-    KLE_ARG(E >= 1 && N >= 1 && m->ext_begin == 0 && m->node_begin == 0 && m->ext_end == N, "unexpected one-rank layout");
-    if (E * nn >= INT32_MAX || N * std::max(dim, cw) >= INT32_MAX)
-        return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
-    if ((int64_t)m->dir.size() != N) return fail(KLE_ERR_SIZ, "element operator: Dirichlet flags do not match the mesh");
+    ElemLayout L;
+    KLE_TRY(elem_layout(ctx, m, std::max(dim, cw), &L));
+    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+    const int64_t E = L.E, N = L.N;
+    if ((int64_t)m->dir.size() != L.next)
+        return fail(KLE_ERR_SIZ, "element operator: Dirichlet flags do not match the mesh");
 
-    // tables (host), validated before upload
-    std::vector<int64_t> conn64((size_t)E * nn);
-    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
-    std::vector<int32_t> conn((size_t)E * nn), inc((size_t)N * maxinc, -1);
-    std::vector<uint8_t> cnt((size_t)N, 0);
-    for (int64_t k = 0; k < E * nn; ++k) {
-        const int64_t g = conn64[k];
-        if (g < 0 || g >= N)
-            return fail(KLE_ERR_OUTOFRANGE, "element operator: connectivity entry %lld outside the mesh", (long long)k);
-        conn[k] = (int32_t)g;
-        if (cnt[g] >= maxinc)
-            return fail(KLE_ERR_OUTOFRANGE, "element operator: node %lld lies in more than %d elements", (long long)g, maxinc);
-        inc[g * maxinc + cnt[g]++] = (int32_t)k;  // k = e * nn + l, ascending e
-    }
-    KLE_TRY(elem_validate(conn, inc, N, E, nn, maxinc));
+    // tables (host) in ext-local node ids, validated before upload
+    std::vector<int32_t> conn, inc;
+    KLE_TRY(elem_tables(m, L, conn, inc));
     // the mask rule folded into the connectivity the GEMM reads: K drops the
-    // Dirichlet entries of x, Krhs the free ones, Rw none
+    // Dirichlet entries of x (ghosts included: m->dir covers the ext range),
+    // Krhs the free ones, Rw none
     if (which != 2)
         for (int64_t k = 0; k < E * nn; ++k)
             if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
 
     KLE_HIP(hipSetDevice(ctx->device));
-    // K_e0 (Rw_e0) through the assembly's own geometry and element kernels
+    // K_e0 (Rw_e0) of global element 0 through the assembly's own geometry and
+    // element kernels
+    kle_mesh m0;
+    first_element_mesh(m, &m0);
     double *dKe = nullptr, *dRwe = nullptr;
-    KLE_TRY(element_first_k(ctx, m, &dKe, which == 2 ? &dRwe : nullptr));
+    KLE_TRY(element_first_k(ctx, &m0, &dKe, which == 2 ? &dRwe : nullptr));
     std::vector<double> kb((size_t)nd * nc);
     hipError_t he = hipMemcpy(kb.data(), which == 2 ? dRwe : dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
     (void)hipFree(dKe);
@@ -433,13 +607,8 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     kle_mat *A = new kle_mat;
     ElemOp *P = new ElemOp;
     A->ctx = ctx;
-    A->kind = 2;
     A->elem = P;
-    A->R = dim;
-    A->C = cw;
-    A->nrows = N;
-    A->m_global = A->m_local = N * dim;
-    A->n_global = A->n_local = N * cw;
+    elem_mat_fields(A, m, L, dim, cw);
     P->which = which;
     P->dim = dim;
     P->cw = cw;
@@ -453,8 +622,9 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     P->N = N;
     // element columns per held K_e0 operand: two tiles of 16 where that still
     // gives every CU a workgroup, else one (four would spill the operand
-    // double buffer out of 256 VGPRs)
+    // double buffer out of 256 VGPRs); E the local elements
     const int64_t nrg = (ndp + EG_ROWS - 1) / EG_ROWS;
+    P->rg_top = (nd - nd / m->ngl) / EG_ROWS;
     P->nct = (E + 31) / 32 * nrg >= ctx->num_cus ? 2 : 1;
     auto up = [&](auto **dp, const void *src, size_t bytes) {
         if (hipMalloc(dp, bytes) != hipSuccess) {
@@ -468,7 +638,7 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     if (!rc && !kdiag.empty()) rc = up(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
-    if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);
+    if (!rc) rc = up(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nd);
     if (rc) {
         kle_mat_destroy(A);

@@ -206,6 +206,9 @@ struct kle_mat {
     int kind = 0;  // 0 node-block, 1 scalar AIJ, 2 element-wise (no stored values: elem)
     kle::ElemOp *elem = nullptr;  // kind 2
     kle::CollocOp *colloc = nullptr;  // kind 2, instead of elem: Curl / SrT / DivSrT (kle_colloc.hip)
+    // kind 2: el_n local elements -- [0, el_ghost) the ghost layer below, [el_ghost, el_int1) those reading
+    // owned nodes alone (run beside the halo), [el_int1, el_n) the top layer reading the upper ghost plane
+    int64_t el_n = 0, el_ghost = 0, el_int1 = 0;
     int halo_overlap = 1;          // N>1: interior rows run while the halo is in flight
     int64_t int_lo = 0, int_hi = 0;  // rows [int_lo, int_hi) read no ghost entries
     int64_t row_lat[3] = {1, 1, 1};  // lattice of the owned rows (x, y, z extents)
@@ -409,17 +412,32 @@ int halo_reverse_plan(kle_ctx *ctx, const HaloPlan &P, int64_t hi0, int bs, cons
                       hipStream_t st);  // kle_core.hip
 // element-wise operator (kle_elem.hip; kle_mat kind 2)
 int element_first_k(kle_ctx *ctx, const kle_mesh *m, double **dKe, double **dRwe_out = nullptr);  // kle_assemble.hip
-int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+// (local: this rank's launches without the halo -- kle_mat_time_local_spmv)
+int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local = false);
 int elem_diagonal(const kle_mat *A, kle_vec *d);
 void elem_drop(kle_mat *A);
 double elem_spmv_bytes(const kle_mat *A);
 std::string elem_kernel_name(const kle_mat *A);
-int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, int64_t N, int64_t E, int nn,
+// a rank's part of a box mesh as the element-wise operators see it
+struct ElemLayout {
+    int64_t N = 0, next = 0, own0 = 0;  // owned nodes, ext nodes, ext-local index of the first owned node
+    int64_t E = 0;                      // local elements: every element touching an owned node
+    int64_t eghost = 0;                 // [0, eghost): the ghost layer below, gathered at its top plane only
+    int64_t eint1 = 0;                  // [eghost, eint1): elements reading owned nodes alone; [eint1, E): the top layer
+    int ltop = 0;                       // first element-local node of an element's top plane
+};
+int elem_layout(const kle_ctx *ctx, const kle_mesh *m, int bw, ElemLayout *out);
+int elem_tables(const kle_mesh *m, const ElemLayout &L, std::vector<int32_t> &conn, std::vector<int32_t> &inc);
+int elem_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &inc, const ElemLayout &L, int nn,
                   int maxinc);
+void elem_mat_fields(kle_mat *A, const kle_mesh *m, const ElemLayout &L, int R, int C);
+void first_element_mesh(const kle_mesh *m, kle_mesh *o);
+int elem_ranges(kle_mat *A, const kle_vec *x, bool local, const std::function<int(int64_t, int64_t, bool)> &launch);
+int elem_check_vecs(const kle_mat *A, const kle_vec *x, const kle_vec *y, const char *what);
 // element-wise collocation operators (kle_colloc.hip; kle_mat kind 2 with colloc set)
 int element_ops(kle_ctx *ctx, const kle_mesh *m, int64_t e, std::vector<double> &geo, std::vector<double> &dh,
                 std::vector<double> *curl, std::vector<double> *srt, std::vector<double> *div);  // kle_assemble.hip
-int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local = false);
 void colloc_drop(kle_mat *A);
 double colloc_spmv_bytes(const kle_mat *A);
 std::string colloc_kernel_name(const kle_mat *A);
@@ -471,6 +489,7 @@ struct Tuning {
     int spmv_brick_pair = 1;  // brick SpMV (read at build): rows in units of two whose tails share one 64-lane item
     int spmv_brick_singles = 1;  // brick SpMV (read at build): rows of one stored block formed by the gather, not as 64-lane items of the bricks
     int spmv_brick_split = 0;  // brick SpMV (read at build): force nbx + 100 nby + 10000 nbz bricks (0: planned)
+    int elem_ghost_rows = 1;  // element-wise K / Krhs / Rw on N > 1: a ghost-layer element's GEMM covers the 128-row groups holding its top-plane rows alone (1); 0 every group (same bits: the other rows are never gathered)
     int spmv_sym_brick = 1;   // box symmetric storage, one rank (read at build): one brick per CU, sums in LDS for the whole stream (kle_brick.hip); 0 the 128-row tiles
 #ifdef KLE_PROBE_BUILD
     // timing probes (wrong results on purpose), compiled only into the probe

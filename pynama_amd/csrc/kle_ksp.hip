@@ -1154,10 +1154,10 @@ static void free_work(kle_ksp *k)
 
 static int make_vec_like_cols(kle_ksp *k, kle_vec **out)
 {
-    // a vector in the column space of A (ghosted for nb matrices)
+    // a vector in the column space of A (ghosted for nb matrices and element-wise operators)
     kle_mat *A = k->A;
-    KLE_TRY(vec_alloc(k->ctx, A->n_local, A->n_global, A->col_lo, A->kind == 0 ? A->ghost_lo : 0,
-                      A->kind == 0 ? A->ghost_hi : 0, out));
+    KLE_TRY(vec_alloc(k->ctx, A->n_local, A->n_global, A->col_lo, A->kind != 1 ? A->ghost_lo : 0,
+                      A->kind != 1 ? A->ghost_hi : 0, out));
     (*out)->bs = A->C;
     (*out)->lo_rank = A->lo_rank;
     (*out)->hi_rank = A->hi_rank;

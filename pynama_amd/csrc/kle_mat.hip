@@ -636,6 +636,10 @@ bool spmv_uses_comm_stream(const kle_mat *A, const kle_vec *x)
     // gsym_spmv)
     if (A->kind == 0 && A->d_sval && g_tune.spmv_sym && A->sym_graph)
         return A->ctx->nranks > 1 && A->halo_overlap != 0;
+    // (an element-wise operator: where it has elements that read no ghost node)
+    if (A->kind == 2)
+        return A->ctx->nranks > 1 && A->halo_overlap && A->el_ghost < A->el_int1 &&
+               (x->lo_rank >= 0 || x->hi_rank >= 0);
     return A->kind == 0 && A->ctx->nranks > 1 && A->halo_overlap &&
            (A->int_lo < A->int_hi || (A->d_sval && g_tune.spmv_sym)) &&
            (x->lo_rank >= 0 || x->hi_rank >= 0 || (x->plan && !x->plan->peers.empty()));
@@ -1648,10 +1652,16 @@ int kle_mat_spmv_bytes(const kle_mat *A, double *bytes)
 int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, double *ms)
 {
     KLE_ARG(A && x && y && ms && reps >= 1, "bad arg");
-    KLE_NO_ELEM(A, "local product timing");
     KLE_TRY(check_mult_layout(A, x, y));
-    KLE_ARG(spmv_can_split(A), "local product timing: box-brick symmetric storage only");
+    KLE_ARG(A->kind == 2 || spmv_can_split(A),
+            "local product timing: box-brick symmetric storage or an element-wise operator only");
     kle_ctx *c = A->ctx;
+    // an element-wise operator: this rank's element launches and its gather
+    auto local = [&]() {
+        return A->kind != 2 ? brick_spmv_local(A, x, y)
+               : A->colloc  ? colloc_spmv(A, x, y, nullptr, true)
+                            : elem_spmv(A, x, y, nullptr, true);
+    };
     hipEvent_t e0, e1;
     KLE_HIP(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) {
@@ -1659,7 +1669,7 @@ int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, 
         return fail(KLE_ERR_DEVICE, "event create failed");
     }
     int rc = hipEventRecord(e0, c->stream) == hipSuccess ? 0 : fail(KLE_ERR_DEVICE, "event record failed");
-    for (int i = 0; i < reps && !rc; ++i) rc = brick_spmv_local(A, x, y);
+    for (int i = 0; i < reps && !rc; ++i) rc = local();
     float t = 0.0f;
     if (!rc && (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                 hipEventElapsedTime(&t, e0, e1) != hipSuccess))

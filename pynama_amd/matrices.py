@@ -50,7 +50,8 @@ class MatFS:
     def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None):
         """kleType (default: -kle_mat_type, default "assembled"): "element"
         builds K, Krhs and Rw as element-wise operators and assembles nothing
-        (uniform box meshes on one rank; anything else raises Error 56).
+        (uniform box meshes, one rank or slabs on several; anything else
+        raises Error 56).
         opType (default: -kle_op_type, default "assembled"): "element" does the
         same for Curl, SrT and DivSrT; with both, nothing at all is assembled."""
         if self.dom.getBoundaryType() != "FS":
@@ -101,7 +102,8 @@ class MatFS:
 
     def getElementK(self):
         """K as an element-wise operator (Mat.createKLEElement): no assembled
-        values, uniform box meshes on one rank.  Created on first use."""
+        values, uniform box meshes (one rank or slabs on several).  Created on
+        first use."""
         if getattr(self, "_elemK", None) is None:
             self._elemK = Mat.createKLEElement(self.dom.getMesh(), "K")
         return self._elemK
@@ -186,7 +188,8 @@ class Operators:
     the per-cell setValues loop; same pattern (explicit zeros kept) and the
     same ascending-cell ADD order.  With opType "element" (-kle_op_type
     element) nothing is assembled: the three are element-wise operators
-    (Mat.createOperatorElement; uniform box meshes on one rank)."""
+    (Mat.createOperatorElement; uniform box meshes, one rank or slabs on
+    several)."""
 
     def __init__(self):
         self.Curl = self.SrT = self.DivSrT = None

@@ -343,8 +343,11 @@ class Mat:
         the product is formed from the mesh's one element matrix, no assembled
         values.  Rw is [dim N x dim_w N] (dim_w = 1 in 2-D, 3 in 3-D).  mult, *,
         multAdd, createVecLeft/Right, getDiagonal (K, Krhs), the size getters,
-        getInfo and spmvKernel work; calls that need stored values raise
-        Error 56, as do unstructured, no-slip and multi-rank meshes."""
+        getInfo, spmvKernel and timeLocalSpmv work, on one rank and on the slab
+        partition of several (owned rows bit-identical to the one-rank
+        product); calls that need stored values raise Error 56, as do
+        unstructured and no-slip meshes and a mesh partitioned for another
+        rank count than the context's."""
         kinds = {"K": 0, "Krhs": 1, "Rw": 2}
         if which not in kinds:
             raise Error(62, f"createKLEElement: which must be 'K', 'Krhs' or 'Rw', not {which!r}")
@@ -363,9 +366,11 @@ class Mat:
         mesh's one element, no assembled values.  Curl is [dim_w N x dim N], SrT
         [dim_s N x dim N], DivSrT [dim N x dim_s N].  mult, *, multAdd,
         createVecLeft/Right, the size getters, getInfo and spmvKernel work;
-        calls that need stored values, getDiagonal and KSP.setOperators raise
-        Error 56, as do unstructured and multi-rank meshes.  No Dirichlet set
-        is needed and no-slip box meshes are accepted."""
+        one rank or the slab partition of several; calls that need stored
+        values, getDiagonal and KSP.setOperators raise Error 56, as do
+        unstructured meshes and a mesh partitioned for another rank count than
+        the context's.  No Dirichlet set is needed and no-slip box meshes are
+        accepted."""
         kinds = {"Curl": 0, "SrT": 1, "DivSrT": 2}
         if which not in kinds:
             raise Error(62, f"createOperatorElement: which must be 'Curl', 'SrT' or 'DivSrT', not {which!r}")
@@ -559,8 +564,9 @@ class Mat:
 
     def timeLocalSpmv(self, x, y, reps=50):
         """Average device ms of `reps` rank-local products (kle_mat_time_local_spmv:
-        the bricks and their gather, no halo either way; no PETSc counterpart) --
-        a part's own kernel time, for ranks that take turns on one GPU."""
+        the bricks and their gather, or an element-wise operator's element
+        launches and gather, no halo either way; no PETSc counterpart) -- a
+        part's own kernel time, for ranks that take turns on one GPU."""
         ms = C.c_double()
         call("kle_mat_time_local_spmv", self._h, x._h, y._h, int(reps), C.byref(ms))
         return ms.value

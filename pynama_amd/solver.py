@@ -45,8 +45,8 @@ class KleSolver:
         K = self.mat.K
         # -kle_k_type element: the KSP's operator and rhs()'s Krhs and Rw are the
         # element-wise operators (MatFS.getElementK / getElementKrhs /
-        # getElementRw); whatever they refuse (unstructured, no-slip, several
-        # ranks) raises -- no fallback.  After a matrix-free build
+        # getElementRw); whatever they refuse (unstructured, no-slip) raises --
+        # no fallback.  After a matrix-free build
         # (-kle_mat_type element) mat.K, mat.Krhs and mat.Rw are those already.
         ktype = Options().getString("kle_k_type", "assembled")
         if ktype not in ("assembled", "element"):
