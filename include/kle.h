@@ -407,6 +407,46 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * unstructured meshes, no-slip meshes and a mesh whose nranks is not the
  * context's. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* Element-wise no-slip operator of a uniform box mesh: the matrices of
+ * kle_assemble_ns (MatNS.buildNS, mat_ns.py:47-145) with no stored values.
+ * which: 0 K, 1 Krhs, 2 Rw, 3 Kfs, 4 Krhsfs, 5 Rwfs, 6 K + Kfs (the operator
+ * of KleSolver.solverFS).  The masks act per velocity DoF through the mesh's
+ * classes F (free) / T (tangential) / N (normal).  Every operator is
+ * S_e^T K_e0 S_e (Rw, Rwfs: S_e^T Rw_e0 S_e^w) restricted to at most two
+ * passes of (column classes kept -> row classes that take the sum), with a
+ * fixed rule on every other row:
+ *     K       {F} -> {F};                       T, N: y_i = x_i
+ *     Krhs    {T,N} -> {F}, negated;            T, N: y_i = x_i
+ *     Rw      every w column -> {F};            T, N: 0
+ *     Kfs     {F,T} -> {T} and {T} -> {F};      T rows also add -x_i; N: 0
+ *     Krhsfs  {N} -> {F,T}, negated;            N: y_i = x_i
+ *     Rwfs    every w column -> {T};            F, N: 0
+ *     K + Kfs {F,T} -> {F,T};                   N: y_i = x_i
+ * Dropping a column is selection: the entry of x is never read, so an Inf or
+ * NaN in it reaches no result.  An identity row returns x_i bit for bit, a
+ * zero row +0.0 and reads nothing.  A pass is one launch of the element GEMM
+ * of kle_mat_create_kle_element whose column index comes from a per-element,
+ * per-column table [E][nc] of ext-local x indices (-1 dropped) instead of the
+ * node connectivity (Rw and Rwfs keep every column and use the node table);
+ * Kfs runs two passes into two result arrays.  A gather per owned DoF applies
+ * its class's rule, the sums in ascending element order: no atomics, bitwise
+ * repeatable.  K + Kfs forms the element sums, where the assembled matrix
+ * carries PETSc's 1 + (S - 1) on tangential diagonals: they differ by at most
+ * eps S |x_i| per row.
+ * kle_mat_get_diagonal: the element diagonal sums in gather order on the
+ * summed rows of K and K + Kfs, those sums - 1 on Kfs's T rows, 0 on every
+ * other summed or zero row, 1 on identity rows; refused for Rw and Rwfs.
+ * kle_mat_copy_dirichlet_rows copies the identity rows (K + Kfs: the N DoFs).
+ * Everything else -- the supported and refused calls, the Krylov solvers, the
+ * several-rank layout with one forward halo beside the interior elements and
+ * owned rows bit-identical to the one-rank product -- is as for
+ * kle_mat_create_kle_element; ghost DoFs are masked through the ext-indexed
+ * classes.  Each operator owns its tables and workspace.
+ * Needs a box mesh with its no-slip DoFs set (kle_mesh_set_noslip_*).
+ * KLE_ERR_SUP for an unstructured mesh, a free-slip mesh and a mesh whose
+ * nranks is not the context's; KLE_ERR_ARG for a bad which.  Every index
+ * table entry and class is checked on the host before upload. */
+int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Element-wise collocation operator of a uniform box mesh: which 0 Curl
  * [dim_w N x dim N], 1 SrT [dim_s N x dim N], 2 DivSrT [dim N x dim_s N], the
  * operators kle_assemble_operators assembles, with no stored values:
@@ -448,7 +488,8 @@ int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_ma
 int kle_element_ops(kle_ctx *ctx, kle_mesh *m, int64_t e, double *Curl_e, double *SrT_e, double *DivSrT_e,
                     double *c_e);
 /* dst_i = src_i on the Dirichlet rows of an element-wise operator (its own
- * Dirichlet flags; rows dim N), every other entry of dst untouched; on the
+ * Dirichlet flags; rows dim N; a no-slip operator of kle_mat_create_ns_element:
+ * its identity rows by DoF class), every other entry of dst untouched; on the
  * context's stream, no synchronisation.  KleSolver uses it after a
  * matrix-free solve: the unit Dirichlet rows make u_i = b_i = u_bc exactly,
  * which a Krylov iteration started from 0 reaches only to its tolerance.

@@ -125,6 +125,7 @@ _SIGS = {
     "kle_assemble_operators": [vp, vp, pvp, pvp, pvp],
     "kle_assemble_ns": [vp, vp] + [pvp] * 9,
     "kle_mat_create_kle_element": [vp, vp, C.c_int, pvp],
+    "kle_mat_create_ns_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_operator_element": [vp, vp, C.c_int, pvp],
     "kle_element_ops": [vp, vp, C.c_int64, f64p, f64p, f64p, f64p],
     "kle_mat_copy_dirichlet_rows": [vp, vp, vp],

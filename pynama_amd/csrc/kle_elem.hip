@@ -53,6 +53,27 @@
 // global element 0 on every rank and neither the per-element accumulation nor
 // the ascending-element gather depends on the partition, so a rank's owned
 // rows are the one-rank product's bit for bit.
+//
+// No-slip meshes (kle_mat_create_ns_element): the seven matrices of
+// MatNS.buildNS (mat_ns.py:47-145) are the same sums with masks per velocity
+// DoF -- classes F / T / N from the mesh's dof_cls -- instead of per node, and
+// Kfs's kept columns depend on the row's class.  Each is at most two passes of
+// (column classes kept -> row classes taking the sum) and a fixed rule on every
+// other row (NS_SPECS below):
+//
+//   k_elem_gemm<CW, NCT, DOF = true>  the same kernel with its column index
+//                  from a per-element, per-column table [E][nc] of ext-local x
+//                  indices (-1 dropped) instead of the node table [E][nn]; a
+//                  second pass is the same launch over a second table into a
+//                  second result array (Kfs only).  Rw and Rwfs keep every
+//                  column and run the per-node kernel unchanged.
+//   k_elem_gather_cls  one thread per owned DoF; the rule byte of its class
+//                  says zero (+0.0, nothing read), identity (x_i bit for bit),
+//                  the sum from pass 0 or from pass 1 (incidence-table order,
+//                  no atomics) and whether -x_i is added (Kfs's T rows).
+//
+// Ghost DoFs are masked through the ext-indexed classes; layout, element
+// ranges, halo and the ghost layer's row groups are those above.
 #include <algorithm>
 #include <cstring>
 
@@ -70,7 +91,20 @@ struct ElemOp {
     int32_t *d_conn = nullptr;  // [E][nn] element -> ext-local node, tensor order; -1 where the operator drops the entry
     int32_t *d_inc = nullptr;   // [N][maxinc] owned node -> e * nn + l, ascending e, -1 padded
     uint8_t *d_dir = nullptr;   // [N] Dirichlet flag of the owned nodes
+    int negate = 0;             // the GEMM stores -K_e0 x_e (Krhs, Krhsfs)
+    // no-slip operators (kle_mat_create_ns_element): masks per velocity DoF
+    int ns = 0;                 // 1: rows by DoF class (k_elem_gather_cls), which = 0 .. 6
+    int npass = 1;              // GEMM passes (Kfs: 2), pass p over d_cidx[p] into d_wsp[p]
+    bool dofcols = false;       // columns through the per-DoF tables d_cidx (Rw, Rwfs: the node table d_conn)
+    int32_t *d_cidx[2] = {nullptr, nullptr};  // [E][nc] element column -> ext-local x index, -1 dropped
+    double *d_wsp[2] = {nullptr, nullptr};    // [E][nd] per pass (d_wsp[0] == d_ws)
+    uint8_t *d_cls = nullptr;   // [N * dim] class of the owned DoFs
+    unsigned rules = 0;         // row rule of class c in byte c (NS_*)
+    unsigned drules = 0;        // diagonal of class c in byte c: 0 zero, 1 one, 2 the element sums, 3 the sums - 1
 };
+
+// row rule of a DoF class: what the class gather writes
+enum : unsigned { NS_ZERO = 0, NS_IDENT = 1, NS_SUM0 = 2, NS_SUM1 = 3, NS_KIND = 3, NS_MINUS_X = 4 };
 
 constexpr int EG_KC = 64;            // k rows of X per LDS chunk
 constexpr int EG_TR = 2;             // 16-row tiles per wave
@@ -78,7 +112,10 @@ constexpr int EG_ROWS = 4 * EG_TR * 16;  // rows per workgroup
 
 typedef double edbl4 __attribute__((ext_vector_type(4)));
 
-template <int CW, int NCT>
+// DOF: the column index comes from a per-element, per-column table [E][nc] of
+// ext-local x indices (-1 dropped) in mconn -- the no-slip masks act per
+// velocity DoF, not per node; everything else is the same kernel.
+template <int CW, int NCT, bool DOF = false>
 __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd, int ndp, int nc, int ncp, int64_t eb,
                                                       int64_t E, int rg0, const double *__restrict__ kt,
                                                       const int32_t *__restrict__ mconn,
@@ -115,14 +152,18 @@ __global__ __launch_bounds__(256, 2) void k_elem_gemm(int negate, int nn, int nd
 #pragma unroll
         for (int i = 0; i < NPT; ++i) {
             const int64_t e = e0 + wv + 4 * i;
-            nr[i] = g < nc && e < E ? mconn[e * nn + l] : -1;
+            if constexpr (DOF) nr[i] = g < nc && e < E ? mconn[e * nc + g] : -1;
+            else nr[i] = g < nc && e < E ? mconn[e * nn + l] : -1;
         }
     };
     auto fetch_x = [&](int k0) {
         const int g = k0 + lane;
         const int a = g - (g / CW) * CW;
 #pragma unroll
-        for (int i = 0; i < NPT; ++i) xr[i] = nr[i] >= 0 ? x[(int64_t)nr[i] * CW + a] : 0.0;
+        for (int i = 0; i < NPT; ++i) {
+            if constexpr (DOF) xr[i] = nr[i] >= 0 ? x[nr[i]] : 0.0;
+            else xr[i] = nr[i] >= 0 ? x[(int64_t)nr[i] * CW + a] : 0.0;
+        }
     };
     // (a tile beyond the last re-reads the wave's first: its sums are never stored)
     auto fetch_a = [&](int k0, double (&t)[EG_TR][KS]) {
@@ -243,6 +284,84 @@ __global__ __launch_bounds__(256) void k_elem_copy_dirichlet(int64_t n, int dim,
     if (dir[i / dim]) dst[i] = src[i];
 }
 
+// No-slip operators: one thread per owned DoF, its row by the rule byte of its
+// class (MatNS.buildNS, mat_ns.py:47-145) -- zero (+0.0, nothing read), the
+// identity (x_i bit for bit) or the sum of its node's incidence entries from
+// the element results of pass 0 or pass 1, in table (ascending element) order
+// like k_elem_gather; NS_MINUS_X adds -x_i (the -1 on Kfs's tangential
+// diagonal).  x is null where the column space is the vorticity's (Rw, Rwfs:
+// no rule of theirs reads it).
+template <int DIM>
+__global__ __launch_bounds__(256) void k_elem_gather_cls(int64_t N, int nn, int nd, int maxinc, unsigned rules,
+                                                         const int32_t *__restrict__ inc,
+                                                         const uint8_t *__restrict__ cls,
+                                                         const double *__restrict__ ws0,
+                                                         const double *__restrict__ ws1,
+                                                         const double *__restrict__ x, double *__restrict__ y,
+                                                         const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const unsigned r = (rules >> (8 * cls[i])) & 0xffu, kind = r & NS_KIND;
+    if (kind == NS_ZERO) {
+        y[i] = 0.0;
+        return;
+    }
+    if (kind == NS_IDENT) {
+        y[i] = x[i];
+        return;
+    }
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    const double *__restrict__ ws = kind == NS_SUM0 ? ws0 : ws1;
+    double s = 0.0;
+    for (int j = 0; j < maxinc; ++j) {
+        const int t = inc[node * maxinc + j];
+        if (t < 0) break;
+        const int e = t / nn, l = t - e * nn;
+        s += ws[(int64_t)e * nd + l * DIM + a];
+    }
+    if (r & NS_MINUS_X) s += -x[i];
+    y[i] = s;
+}
+
+// diagonal by class: 0, 1 (identity rows), the incident elements' K_e0
+// diagonal entries in gather order (a summed row whose own class is a kept
+// column), those sums + (-1) (Kfs's tangential rows)
+template <int DIM>
+__global__ __launch_bounds__(256) void k_elem_diag_cls(int64_t N, int nn, int maxinc, unsigned drules,
+                                                       const int32_t *__restrict__ inc,
+                                                       const uint8_t *__restrict__ cls,
+                                                       const double *__restrict__ kdiag, double *__restrict__ d)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const unsigned r = (drules >> (8 * cls[i])) & 0xffu;
+    if (r < 2) {
+        d[i] = r ? 1.0 : 0.0;
+        return;
+    }
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    double s = 0.0;
+    for (int j = 0; j < maxinc; ++j) {
+        const int t = inc[node * maxinc + j];
+        if (t < 0) break;
+        s += kdiag[(t % nn) * DIM + a];
+    }
+    d[i] = r == 3 ? s + (-1.0) : s;
+}
+
+// dst_i = src_i on the identity rows of a no-slip operator, nothing else touched
+__global__ __launch_bounds__(256) void k_elem_copy_ident_cls(int64_t n, unsigned rules, const uint8_t *__restrict__ cls,
+                                                             const double *__restrict__ src, double *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (((rules >> (8 * cls[i])) & NS_KIND) == NS_IDENT) dst[i] = src[i];
+}
+
 // Every index the device tables hold, checked on the host before upload: a
 // bad table is an error code, never an out-of-range access.
 // conn holds ext-local node ids in [0, next); inc covers the owned nodes, ext
@@ -296,8 +415,24 @@ static void launch_gemm(const ElemOp *P, int64_t e0, int64_t e1, int rg0, hipStr
     const int ne = 16 * P->nct;
     dim3 grid((unsigned)((e1 - e0 + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS - rg0));
 #define KLE_ELEM_GEMM(NCT)                                                                                      \
-    hipLaunchKernelGGL((k_elem_gemm<CW, NCT>), grid, dim3(256), 0, st, P->which == 1, P->nn, P->nd, P->ndp, P->nc, \
+    hipLaunchKernelGGL((k_elem_gemm<CW, NCT>), grid, dim3(256), 0, st, P->negate, P->nn, P->nd, P->ndp, P->nc, \
                        P->ncp, e0, e1, rg0, P->d_kt, P->d_conn, x, P->d_ws, istate)
+    if (P->nct == 2) KLE_ELEM_GEMM(2);
+    else KLE_ELEM_GEMM(1);
+#undef KLE_ELEM_GEMM
+}
+
+// pass p of a no-slip operator with per-DoF columns: the same launch over the
+// pass's index table and result array
+template <int CW>
+static void launch_gemm_dof(const ElemOp *P, int p, int64_t e0, int64_t e1, int rg0, hipStream_t st, const double *x,
+                            const int *istate)
+{
+    const int ne = 16 * P->nct;
+    dim3 grid((unsigned)((e1 - e0 + ne - 1) / ne), (unsigned)((P->ndp + EG_ROWS - 1) / EG_ROWS - rg0));
+#define KLE_ELEM_GEMM(NCT)                                                                                       \
+    hipLaunchKernelGGL((k_elem_gemm<CW, NCT, true>), grid, dim3(256), 0, st, P->negate, P->nn, P->nd, P->ndp, P->nc, \
+                       P->ncp, e0, e1, rg0, P->d_kt, P->d_cidx[p], x, P->d_wsp[p], istate)
     if (P->nct == 2) KLE_ELEM_GEMM(2);
     else KLE_ELEM_GEMM(1);
 #undef KLE_ELEM_GEMM
@@ -354,6 +489,15 @@ int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool 
     hipStream_t st = A->ctx->stream;
     KLE_TRY(elem_ranges(A, x, local, [&](int64_t e0, int64_t e1, bool ghost) -> int {
         const int rg0 = ghost && g_tune.elem_ghost_rows ? P->rg_top : 0;
+        if (P->dofcols) {
+            // (per-DoF columns: the column space is the velocity's, cw = dim)
+            for (int p = 0; p < P->npass; ++p) {
+                if (P->cw == 2) launch_gemm_dof<2>(P, p, e0, e1, rg0, st, x->base, istate);
+                else launch_gemm_dof<3>(P, p, e0, e1, rg0, st, x->base, istate);
+            }
+            KLE_HIP(hipGetLastError());
+            return 0;
+        }
         if (P->cw == 1) launch_gemm<1>(P, e0, e1, rg0, st, x->base, istate);
         else if (P->cw == 2) launch_gemm<2>(P, e0, e1, rg0, st, x->base, istate);
         else launch_gemm<3>(P, e0, e1, rg0, st, x->base, istate);
@@ -362,6 +506,18 @@ int elem_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool 
     }));
     const int64_t n = P->N * P->dim;
     dim3 gg((unsigned)((n + 255) / 256));
+    if (P->ns) {
+        // (Rw, Rwfs: x is the vorticity -- their rules, zero and sum, never read it)
+        const double *xv = P->dofcols ? x->d : nullptr;
+        if (P->dim == 2)
+            hipLaunchKernelGGL(k_elem_gather_cls<2>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->rules,
+                               P->d_inc, P->d_cls, P->d_wsp[0], P->d_wsp[1], xv, y->d, istate);
+        else
+            hipLaunchKernelGGL(k_elem_gather_cls<3>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->rules,
+                               P->d_inc, P->d_cls, P->d_wsp[0], P->d_wsp[1], xv, y->d, istate);
+        KLE_HIP(hipGetLastError());
+        return 0;
+    }
     const double *xd = P->which == 2 ? nullptr : x->d;  // Rw: no Dirichlet diagonal, x is never read by the gather
     if (P->dim == 2)
         hipLaunchKernelGGL(k_elem_gather<2>, gg, dim3(256), 0, st, P->N, P->nn, P->nd, P->maxinc, P->d_inc, P->d_dir,
@@ -377,11 +533,19 @@ int elem_diagonal(const kle_mat *A, kle_vec *d)
 {
     const ElemOp *P = A->elem;
     if (!P) return fail(KLE_ERR_STATE, "element operator without tables");
-    if (P->which == 2) return fail(KLE_ERR_SUP, "getDiagonal: the element-wise Rw is rectangular");
+    if (P->ns ? !P->dofcols : P->which == 2)
+        return fail(KLE_ERR_SUP, "getDiagonal: the element-wise Rw is rectangular");
     hipStream_t st = A->ctx->stream;
     const int64_t n = P->N * P->dim;
     dim3 gg((unsigned)((n + 255) / 256));
-    if (P->dim == 2)
+    if (P->ns) {
+        if (P->dim == 2)
+            hipLaunchKernelGGL(k_elem_diag_cls<2>, gg, dim3(256), 0, st, P->N, P->nn, P->maxinc, P->drules, P->d_inc,
+                               P->d_cls, P->d_kdiag, d->d);
+        else
+            hipLaunchKernelGGL(k_elem_diag_cls<3>, gg, dim3(256), 0, st, P->N, P->nn, P->maxinc, P->drules, P->d_inc,
+                               P->d_cls, P->d_kdiag, d->d);
+    } else if (P->dim == 2)
         hipLaunchKernelGGL(k_elem_diag<2>, gg, dim3(256), 0, st, P->N, P->nn, P->maxinc, P->which, P->d_inc, P->d_dir,
                            P->d_kdiag, d->d);
     else
@@ -402,6 +566,10 @@ void elem_drop(kle_mat *A)
     (void)hipFree(P->d_conn);
     (void)hipFree(P->d_inc);
     (void)hipFree(P->d_dir);
+    (void)hipFree(P->d_cidx[0]);
+    (void)hipFree(P->d_cidx[1]);
+    (void)hipFree(P->d_wsp[1]);  // (d_wsp[0] is d_ws)
+    (void)hipFree(P->d_cls);
     delete P;
     A->elem = nullptr;
 }
@@ -412,6 +580,10 @@ double elem_spmv_bytes(const kle_mat *A)
 {
     const ElemOp *P = A->elem;
     if (!P) return 0.0;
+    if (P->ns)  // the index tables (per DoF: nc entries per element and pass) and the class bytes instead
+        return 8.0 * P->nd * P->nc + 4.0 * P->E * (P->dofcols ? P->nc * P->npass : P->nn) + 4.0 * P->N * P->maxinc +
+               1.0 * P->N * P->dim + 8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * A->m_local +
+               2.0 * 8.0 * P->E * P->nd * P->npass;
     return 8.0 * P->nd * P->nc + 4.0 * P->E * P->nn + 4.0 * P->N * P->maxinc + 1.0 * P->N +
            8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * A->m_local + 2.0 * 8.0 * P->E * P->nd;
 }
@@ -420,6 +592,9 @@ std::string elem_kernel_name(const kle_mat *A)
 {
     const ElemOp *P = A->elem;
     if (!P) return "?";
+    if (P->ns)
+        return "k_elem_gemm<" + std::to_string(P->cw) + "," + std::to_string(P->nct) + (P->dofcols ? ",1>" : ">") +
+               (P->npass == 2 ? "x2" : "") + "+k_elem_gather_cls<" + std::to_string(P->dim) + ">";
     return "k_elem_gemm<" + std::to_string(P->cw) + "," + std::to_string(P->nct) + ">+k_elem_gather<" +
            std::to_string(P->dim) + ">";
 }
@@ -532,6 +707,51 @@ void first_element_mesh(const kle_mesh *m, kle_mesh *o)
     o->elem_end = 1;
 }
 
+// K_e0 (rw: Rw_e0) of global element 0 through the assembly's own geometry
+// and element kernels: kt zero-padded to ndp x ncp in MFMA operand order,
+// kdiag its diagonal (K_e0 only)
+static int elem_first_operand(kle_ctx *ctx, const kle_mesh *m, bool rw, int cw, std::vector<double> &kt,
+                              std::vector<double> &kdiag)
+{
+    const int dim = m->dim, nn = m->nn(), nd = dim * nn, ndp = (nd + 15) & ~15, nc = cw * nn, ncp = (nc + 3) & ~3;
+    kle_mesh m0;
+    first_element_mesh(m, &m0);
+    double *dKe = nullptr, *dRwe = nullptr;
+    KLE_TRY(element_first_k(ctx, &m0, &dKe, rw ? &dRwe : nullptr));
+    std::vector<double> kb((size_t)nd * nc);
+    hipError_t he = hipMemcpy(kb.data(), rw ? dRwe : dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(dKe);
+    (void)hipFree(dRwe);
+    if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element matrix download failed: %s", hipGetErrorString(he));
+    // blocks [l][m][a][b], b < cw -> K[l dim + a][m cw + b], zero-padded to ndp x ncp, in operand order
+    auto kat = [&](int r, int c) {
+        return kb[(((size_t)(r / dim) * nn + c / cw) * dim + r % dim) * cw + c % cw];
+    };
+    kt.assign((size_t)ndp * ncp, 0.0);
+    kdiag.assign((size_t)(rw ? 0 : nd), 0.0);
+    const int nks = ncp / 4;
+    for (int rt = 0; rt < ndp / 16; ++rt)
+        for (int ks = 0; ks < nks; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int r = rt * 16 + (lane & 15), c = ks * 4 + (lane >> 4);
+                if (r < nd && c < nc) kt[((size_t)rt * nks + ks) * 64 + lane] = kat(r, c);
+            }
+    for (size_t r = 0; r < kdiag.size(); ++r) kdiag[r] = kat((int)r, (int)r);
+    return 0;
+}
+
+// a device array of an element-wise operator, filled from src where given
+template <class T>
+static int elem_upload(T **dp, const void *src, size_t bytes)
+{
+    if (hipMalloc(dp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *dp = nullptr;
+        return fail(KLE_ERR_MEM, "out of device memory for the element-wise operator");
+    }
+    return src ? h2d(*dp, src, bytes) : 0;
+}
+
 }  // namespace kle
 
 using namespace kle;
@@ -546,8 +766,12 @@ extern "C" int kle_mat_copy_dirichlet_rows(const kle_mat *A, const kle_vec *src,
     if (src->n_local != n || dst->n_local != n)
         return fail(KLE_ERR_SIZ, "copyDirichletRows: vectors do not match the operator's rows");
     if (src->d == dst->d) return 0;
-    hipLaunchKernelGGL(k_elem_copy_dirichlet, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, A->ctx->stream, n, P->dim,
-                       P->d_dir, src->d, dst->d);
+    if (P->ns)  // a no-slip operator: its identity rows, by DoF class
+        hipLaunchKernelGGL(k_elem_copy_ident_cls, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, A->ctx->stream, n,
+                           P->rules, P->d_cls, src->d, dst->d);
+    else
+        hipLaunchKernelGGL(k_elem_copy_dirichlet, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, A->ctx->stream, n,
+                           P->dim, P->d_dir, src->d, dst->d);
     KLE_HIP(hipGetLastError());
     return 0;
 }
@@ -579,30 +803,8 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
             if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
 
     KLE_HIP(hipSetDevice(ctx->device));
-    // K_e0 (Rw_e0) of global element 0 through the assembly's own geometry and
-    // element kernels
-    kle_mesh m0;
-    first_element_mesh(m, &m0);
-    double *dKe = nullptr, *dRwe = nullptr;
-    KLE_TRY(element_first_k(ctx, &m0, &dKe, which == 2 ? &dRwe : nullptr));
-    std::vector<double> kb((size_t)nd * nc);
-    hipError_t he = hipMemcpy(kb.data(), which == 2 ? dRwe : dKe, sizeof(double) * kb.size(), hipMemcpyDeviceToHost);
-    (void)hipFree(dKe);
-    (void)hipFree(dRwe);
-    if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element matrix download failed: %s", hipGetErrorString(he));
-    // blocks [l][m][a][b], b < cw -> K[l dim + a][m cw + b], zero-padded to ndp x ncp, in operand order
-    auto kat = [&](int r, int c) {
-        return kb[(((size_t)(r / dim) * nn + c / cw) * dim + r % dim) * cw + c % cw];
-    };
-    std::vector<double> kt((size_t)ndp * ncp, 0.0), kdiag((size_t)(which == 2 ? 0 : nd));
-    const int nks = ncp / 4;
-    for (int rt = 0; rt < ndp / 16; ++rt)
-        for (int ks = 0; ks < nks; ++ks)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = rt * 16 + (lane & 15), c = ks * 4 + (lane >> 4);
-                if (r < nd && c < nc) kt[((size_t)rt * nks + ks) * 64 + lane] = kat(r, c);
-            }
-    for (size_t r = 0; r < kdiag.size(); ++r) kdiag[r] = kat((int)r, (int)r);
+    std::vector<double> kt, kdiag;
+    KLE_TRY(elem_first_operand(ctx, m, which == 2, cw, kt, kdiag));
 
     kle_mat *A = new kle_mat;
     ElemOp *P = new ElemOp;
@@ -610,6 +812,7 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     A->elem = P;
     elem_mat_fields(A, m, L, dim, cw);
     P->which = which;
+    P->negate = which == 1;
     P->dim = dim;
     P->cw = cw;
     P->nn = nn;
@@ -626,20 +829,134 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
     const int64_t nrg = (ndp + EG_ROWS - 1) / EG_ROWS;
     P->rg_top = (nd - nd / m->ngl) / EG_ROWS;
     P->nct = (E + 31) / 32 * nrg >= ctx->num_cus ? 2 : 1;
-    auto up = [&](auto **dp, const void *src, size_t bytes) {
-        if (hipMalloc(dp, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *dp = nullptr;
-            return fail(KLE_ERR_MEM, "out of device memory for the element-wise operator");
+    int rc = elem_upload(&P->d_kt, kt.data(), sizeof(double) * kt.size());
+    if (!rc && !kdiag.empty()) rc = elem_upload(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
+    if (!rc) rc = elem_upload(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
+    if (!rc) rc = elem_upload(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc) rc = elem_upload(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
+    if (!rc) rc = elem_upload(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nd);
+    if (rc) {
+        kle_mat_destroy(A);
+        return rc;
+    }
+    *out = A;
+    return 0;
+}
+
+// The no-slip operators of MatNS.buildNS (mat_ns.py:47-145) in element-wise
+// form.  Every one is S_e^T K_e0 S_e (Rw, Rwfs: S_e^T Rw_e0 S_e^w) restricted
+// to at most two passes of (column classes kept -> row classes taking the sum),
+// with a fixed rule on every other row; classes F / T / N per velocity DoF.
+namespace {
+struct NsSpec {
+    bool rw, negate;
+    int npass;
+    unsigned cols[2];   // column classes pass p keeps (bit c = class c); Rw, Rwfs: every w column
+    unsigned rule[3];   // row rule of F, T, N
+};
+constexpr unsigned CF = 1u << DOF_FREE, CT = 1u << DOF_TANG, CN = 1u << DOF_NORMAL;
+const NsSpec NS_SPECS[7] = {
+    /* K      */ {false, false, 1, {CF, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
+    /* Krhs   */ {false, true, 1, {CT | CN, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
+    /* Rw     */ {true, false, 1, {0, 0}, {NS_SUM0, NS_ZERO, NS_ZERO}},
+    /* Kfs    */ {false, false, 2, {CF | CT, CT}, {NS_SUM1, NS_SUM0 | NS_MINUS_X, NS_ZERO}},
+    /* Krhsfs */ {false, true, 1, {CN, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
+    /* Rwfs   */ {true, false, 1, {0, 0}, {NS_ZERO, NS_SUM0, NS_ZERO}},
+    /* K+Kfs  */ {false, false, 1, {CF | CT, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
+};
+}  // namespace
+
+extern "C" int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which >= 0 && which <= 6, "which must be 0 (K), 1 (Krhs), 2 (Rw), 3 (Kfs), 4 (Krhsfs), 5 (Rwfs) or 6 (K + Kfs)");
+    if (m->kind != 0) return fail(KLE_ERR_SUP, "element-wise operator: needs a uniform box mesh (unstructured mesh given)");
+    if (m->dof_cls.empty())
+        return fail(KLE_ERR_SUP, "element-wise no-slip operator: the mesh has no no-slip DoFs (kle_mesh_set_noslip_*)");
+    const NsSpec &S = NS_SPECS[which];
+    const int dim = m->dim, nn = m->nn(), nd = dim * nn, ndp = (nd + 15) & ~15, maxinc = 1 << dim;
+    const int cw = S.rw ? (dim == 2 ? 1 : 3) : dim, nc = cw * nn, ncp = (nc + 3) & ~3;
+    ElemLayout L;
+    KLE_TRY(elem_layout(ctx, m, std::max(dim, cw), &L));
+    const int64_t E = L.E, N = L.N;
+    if ((int64_t)m->dof_cls.size() != L.next * dim)
+        return fail(KLE_ERR_SIZ, "element operator: DoF classes do not cover the mesh's ext range");
+    for (size_t k = 0; k < m->dof_cls.size(); ++k)
+        if (m->dof_cls[k] > DOF_NORMAL)
+            return fail(KLE_ERR_OUTOFRANGE, "element operator: DoF %lld has the unknown class %d", (long long)k,
+                        (int)m->dof_cls[k]);
+    if (E * nc >= INT32_MAX) return fail(KLE_ERR_SUP, "element-wise operator: the mesh exceeds the 32-bit tables");
+
+    // tables (host) in ext-local ids, validated before upload
+    std::vector<int32_t> conn, inc, cidx[2];
+    KLE_TRY(elem_tables(m, L, conn, inc));
+    if (!S.rw) {
+        // per element and column (l, b): the ext-local x index conn * dim + b where
+        // the pass keeps the DoF's class, else -1 (ghost DoFs: dof_cls covers the ext range)
+        const int64_t xmax = L.next * cw;
+        for (int p = 0; p < S.npass; ++p) {
+            cidx[p].assign((size_t)E * nc, -1);
+            for (int64_t e = 0; e < E; ++e)
+                for (int g = 0; g < nc; ++g) {
+                    const int64_t xi = (int64_t)conn[e * nn + g / dim] * dim + g % dim;
+                    if (xi < 0 || xi >= xmax)
+                        return fail(KLE_ERR_OUTOFRANGE, "element operator: column %d of element %lld outside the x range",
+                                    g, (long long)e);
+                    if ((S.cols[p] >> m->dof_cls[xi]) & 1u) cidx[p][e * nc + g] = (int32_t)xi;
+                }
+            for (int64_t k = 0; k < E * nc; ++k)
+                if (cidx[p][k] < -1 || cidx[p][k] >= xmax)
+                    return fail(KLE_ERR_OUTOFRANGE, "element operator: index table entry %lld = %d outside [-1, %lld)",
+                                (long long)k, cidx[p][k], (long long)xmax);
         }
-        return src ? h2d(*dp, src, bytes) : 0;
-    };
-    int rc = up(&P->d_kt, kt.data(), sizeof(double) * kt.size());
-    if (!rc && !kdiag.empty()) rc = up(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
-    if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
-    if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
-    if (!rc) rc = up(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
-    if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nd);
+    }
+
+    KLE_HIP(hipSetDevice(ctx->device));
+    std::vector<double> kt, kdiag;
+    KLE_TRY(elem_first_operand(ctx, m, S.rw, cw, kt, kdiag));
+
+    kle_mat *A = new kle_mat;
+    ElemOp *P = new ElemOp;
+    A->ctx = ctx;
+    A->elem = P;
+    elem_mat_fields(A, m, L, dim, cw);
+    P->which = which;
+    P->ns = 1;
+    P->negate = S.negate;
+    P->npass = S.npass;
+    P->dofcols = !S.rw;
+    P->dim = dim;
+    P->cw = cw;
+    P->nn = nn;
+    P->nd = nd;
+    P->ndp = ndp;
+    P->nc = nc;
+    P->ncp = ncp;
+    P->maxinc = maxinc;
+    P->E = E;
+    P->N = N;
+    for (int c = 0; c < 3; ++c) {
+        const unsigned r = S.rule[c], kind = r & NS_KIND;
+        P->rules |= r << (8 * c);
+        // the diagonal: a summed row holds its own column where its pass keeps the row's class
+        unsigned d = kind == NS_IDENT ? 1u : 0u;
+        if (kind >= NS_SUM0 && !S.rw && ((S.cols[kind - NS_SUM0] >> c) & 1u)) d = r & NS_MINUS_X ? 3u : 2u;
+        P->drules |= d << (8 * c);
+    }
+    // (element columns per held operand and the ghost layer's row groups: as kle_mat_create_kle_element)
+    const int64_t nrg = (ndp + EG_ROWS - 1) / EG_ROWS;
+    P->rg_top = (nd - nd / m->ngl) / EG_ROWS;
+    P->nct = (E + 31) / 32 * nrg >= ctx->num_cus ? 2 : 1;
+    int rc = elem_upload(&P->d_kt, kt.data(), sizeof(double) * kt.size());
+    if (!rc && !kdiag.empty()) rc = elem_upload(&P->d_kdiag, kdiag.data(), sizeof(double) * kdiag.size());
+    if (!rc && S.rw) rc = elem_upload(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
+    for (int p = 0; p < S.npass && !rc && !S.rw; ++p)
+        rc = elem_upload(&P->d_cidx[p], cidx[p].data(), sizeof(int32_t) * cidx[p].size());
+    if (!rc) rc = elem_upload(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc) rc = elem_upload(&P->d_cls, m->dof_cls.data() + L.own0 * dim, (size_t)N * dim);
+    if (!rc) rc = elem_upload(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nd);
+    P->d_wsp[0] = P->d_ws;
+    if (!rc && S.npass == 2) rc = elem_upload(&P->d_wsp[1], nullptr, sizeof(double) * (size_t)E * nd);
     if (rc) {
         kle_mat_destroy(A);
         return rc;

@@ -36,6 +36,17 @@ def kle_op_type(opType=None):
     return opType
 
 
+def kle_ns_type(nsType=None):
+    """The form of the no-slip KLE matrices (MatNS): the keyword, else
+    -kle_ns_type, else "assembled"; anything but assembled | element raises
+    Error 62."""
+    if nsType is None:
+        nsType = Options().getString("kle_ns_type", "assembled")
+    if nsType not in ("assembled", "element"):
+        raise Error(62, f"-kle_ns_type {nsType}: assembled | element")
+    return nsType
+
+
 class MatFS:
     bcType = "FS"
 
@@ -148,23 +159,44 @@ class MatNS(MatFS):
         self.Kfs = self.Krhsfs = self.Rwfs = self.Rdfs = None
         self._Ksum = None
 
-    def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None):
+    def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None, nsType=None):
         """opType "element" (default: -kle_op_type): Curl, SrT and DivSrT as
-        element-wise operators, which carry no boundary rule; the no-slip KLE
-        matrices themselves have no element-wise form."""
+        element-wise operators, which carry no boundary rule.
+        nsType (default: -kle_ns_type, default "assembled"): "element" builds
+        K, Krhs, Rw, Kfs, Krhsfs, Rwfs and K + Kfs as element-wise operators
+        (Mat.createNSElement) and never calls kle_assemble_ns; Rd and Rdfs are
+        empty assembled matrices and mat.kle keeps its order of eight.  Uniform
+        box meshes, one rank or slabs on several; anything else raises Error
+        56.  This switch is the way to the matrix-free no-slip system:
+        kleType="element" / -kle_mat_type element name the free-slip form,
+        which a no-slip mesh does not have, and keep raising Error 56 here."""
         if kle_mat_type(kleType) == "element":
             raise Error(56, "-kle_mat_type element: no-slip matrices have no element-wise form")
         if self.dom.getBoundaryType() != "NS":
             raise Error(56, "MatNS needs no-slip boundaries")
+        nsType = kle_ns_type(nsType) if buildKLE else nsType
         opType = kle_op_type(opType) if buildOperators else opType
         if buildKLE:
-            self.buildNS()
+            self.buildNS(nsType)
         if buildOperators:
             self.buildOperators(opType)
 
-    def buildNS(self):
+    def buildNS(self, nsType="assembled"):
         ctx = get_ctx()
         mesh = self.dom.getMesh()
+        if nsType == "element":
+            # matrix-free: no kle_assemble_ns, no assembled values
+            dim = self.dom.getDimensions()[0]
+            names = ("K", "Krhs", "Rw", "Kfs", "Krhsfs", "Rwfs", "K+Kfs")
+            ops = {n: Mat.createNSElement(mesh, n) for n in names}
+            for n, m in ops.items():
+                m.setName(n)
+            self.K, self.Krhs, self.Rw = ops["K"], ops["Krhs"], ops["Rw"]
+            self.Kfs, self.Krhsfs, self.Rwfs = ops["Kfs"], ops["Krhsfs"], ops["Rwfs"]
+            self._Ksum = ops["K+Kfs"]
+            self.Rd, self.Rdfs = self._empty(dim), self._empty(dim, "Rdfs")
+            self.kle = [self.K, self.Krhs, self.Rw, self.Rd, self.Kfs, self.Krhsfs, self.Rwfs, self.Rdfs]
+            return
         h = [C.c_void_p() for _ in range(9)]
         call("kle_assemble_ns", ctx.h, mesh._h, *[C.byref(x) for x in h])
         dim, dim_w, _ = self.dom.getDimensions()

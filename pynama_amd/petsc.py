@@ -360,6 +360,29 @@ class Mat:
         return m
 
     @classmethod
+    def createNSElement(cls, mesh, which="K"):
+        """Element-wise no-slip operator of a uniform box mesh
+        (kle_mat_create_ns_element): K, Krhs, Rw, Kfs, Krhsfs, Rwfs or K+Kfs of
+        MatNS.buildNS with the masks acting per velocity DoF (classes free /
+        tangential / normal), formed from the mesh's one element matrix with no
+        assembled values.  Rw and Rwfs are [dim N x dim_w N].  Works like
+        createKLEElement (getDiagonal: K, K+Kfs, Kfs, Krhs, Krhsfs;
+        copyDirichletRows: the operator's identity rows); needs a box mesh
+        with its no-slip DoFs set -- a free-slip box, an unstructured mesh and
+        a mesh partitioned for another rank count raise Error 56, any other
+        `which` Error 62."""
+        kinds = {"K": 0, "Krhs": 1, "Rw": 2, "Kfs": 3, "Krhsfs": 4, "Rwfs": 5, "K+Kfs": 6}
+        if which not in kinds:
+            raise Error(62, f"createNSElement: which must be one of {', '.join(kinds)}, not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_ns_element", ctx.h, mesh._h, kinds[which], C.byref(h))
+        dim_w = 1 if mesh.dim == 2 else 3
+        m = cls._wrap(h, ctx, mesh, mesh.dim, dim_w if which in ("Rw", "Rwfs") else mesh.dim)
+        m.setName("element " + which)
+        return m
+
+    @classmethod
     def createOperatorElement(cls, mesh, which="Curl"):
         """Element-wise Curl, SrT or DivSrT of a uniform box mesh
         (kle_mat_create_operator_element): sum-factorised products from the

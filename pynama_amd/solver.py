@@ -110,6 +110,10 @@ class KleSolver:
 
     def solveFS(self, vort):
         self.solverFS(self.rhsFS(vort), self.__velFS)
+        if self._exactBC:
+            # K + Kfs holds unit rows on the normal DoFs alone; _wtmp is
+            # Krhsfs * vel from rhsFS(), whose normal rows are vel exactly
+            self.mat.getKplusKfs().copyDirichletRows(self._wtmp, self.__velFS)
 
     def getFreeSlipSolution(self):
         return self.__velFS

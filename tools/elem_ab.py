@@ -50,7 +50,24 @@ corners, delta over the 27 first / middle / last elements per axis).  With
 ngl 7) under -kle_mat_type element -kle_op_type element, one evalRHS, its time
 and the device memory held.
 
-  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check] [--matfree | --operators [--config4]]
+With --noslip the legs are those of the matrix-free no-slip system
+(Mat.createNSElement, MatNS.build(nsType="element"); records to
+profiles/elem/noslip.jsonl) on a six-wall lid-driven box at the first mesh (if
+the assembled set cannot be built there, the next smaller of --fallback-meshes
+on which it can, named in every record), in one process:
+
+  build_ns      wall time of MatNS.build(buildOperators=False) and the device
+                memory the eight KLE matrices and K + Kfs hold, nsType assembled
+                and element alternating, after one untimed build of each
+  product_<op>  --reps products of K, K+Kfs, Krhsfs and Rwfs (assembled, element)
+  product_K_dof_vs_node  the per-DoF K against the free-slip element-wise K of
+                the same lattice (all faces Dirichlet): the cost of the [E][nc]
+                index table over the [E][nn] one
+  solve_ns      one solveFS + solve from the element build (wall time,
+                iterations, reasons)
+
+  python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
+                          [--matfree | --operators [--config4] | --noslip]
 """
 import argparse
 import ctypes as C
@@ -536,6 +553,134 @@ def config4(a, pa, np, hip, ctx, emit):
                                    "hold about 320 GB at this size, more than one MI355X's 288 GB"})
 
 
+NS_WALLS = {"up": [1.0, 0.0, 0.0], "down": [0.0, 0.0, 0.0], "left": [0.0, 0.0, 0.0], "right": [0.0, 0.0, 0.0],
+            "front": [0.0, 0.0, 0.0], "back": [0.0, 0.0, 0.0]}
+
+
+def noslip(a, pa, np, hip, ctx, emit):
+    from pynama_amd.petsc import Mat
+
+    def parse(spec):
+        ne_s, ngl = spec.split(":")
+        return [int(v) for v in ne_s.split(",")], int(ngl)
+
+    def domain(nelem, ngl, bc):
+        dom = pa.Domain()
+        dom.configure({"domain": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * 3, "upper": [1.0] * 3}},
+                       "boundary-conditions": bc})
+        dom.setUp()
+        return dom
+
+    def build(dom, kind):
+        mat = pa.MatNS()
+        mat.setDomain(dom)
+        mat.build(buildOperators=False, nsType=kind)
+        ctx.synchronize()
+        return mat
+
+    # the largest candidate mesh on which the assembled set can be built
+    wanted, refused = a.meshes[0], []
+    for spec in [wanted] + list(a.fallback_meshes):
+        nelem, ngl = parse(spec)
+        dom = domain(nelem, ngl, {"no-slip": NS_WALLS})
+        try:
+            build(dom, "assembled")
+            break
+        except pa.Error as e:
+            refused.append({"mesh": spec, "error": str(e)})
+            del dom
+            gc.collect()
+    else:
+        raise SystemExit("elem_ab --noslip: the assembled no-slip set could not be built on any mesh")
+    gc.collect()
+    dim = 3
+    base = {"nelem": nelem, "ngl": ngl, "dofs": dom.mesh.N * dim, "walls": sorted(NS_WALLS), "rounds": a.rounds,
+            "mesh_wanted": wanted, "assembled_refused_on": refused}
+    kinds = ("assembled", "element")
+    mats, t_build, mem = {}, {k: [] for k in kinds}, {}
+    for rnd in range(a.rounds + 1):  # round 0: untimed (module load, first allocations)
+        for kt in kinds:
+            mats.pop(kt, None)
+            gc.collect()
+            ctx.synchronize()
+            m0 = hip.free_bytes()
+            t0 = time.perf_counter()
+            mats[kt] = build(dom, kt)
+            t1 = time.perf_counter()
+            if rnd:
+                t_build[kt].append(1e3 * (t1 - t0))
+                mem[kt] = m0 - hip.free_bytes()
+    for kt in kinds:
+        emit(dict(base, leg="build_ns", nsType=kt, formats=[m.getFormat() for m in mats[kt].kle],
+                  ms=spread(t_build[kt]), device_memory={"bytes_kle_and_Ksum": mem[kt]}))
+    emit(dict(base, leg="ratio_build_ns", assembled_over_element={
+        "build": statistics.median(t_build["assembled"]) / statistics.median(t_build["element"]),
+        "device_memory": mem["assembled"] / max(mem["element"], 1)}))
+
+    def get(mat, nm):
+        return mat.getKplusKfs() if nm == "K+Kfs" else getattr(mat, nm)
+
+    def time_legs(ops, x, y):
+        t = {k: [] for k in ops}
+        for _ in range(a.rounds):
+            for label, A in ops.items():
+                for _w in range(20):
+                    A.mult(x, y)
+                ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                t[label].append(1e3 * ms / a.reps)
+        return t
+
+    for nm in ("K", "K+Kfs", "Krhsfs", "Rwfs"):
+        ops = {kt: get(mats[kt], nm) for kt in kinds}
+        x = ops["element"].createVecRight()
+        x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+        y = ops["element"].createVecLeft()
+        t = time_legs(ops, x, y)
+        for label, A in ops.items():
+            emit(dict(base, leg="product_" + nm, operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                      reps=a.reps, us=spread(t[label])))
+        emit(dict(base, leg="ratio_" + nm, assembled_over_element=statistics.median(t["assembled"]) /
+                  statistics.median(t["element"]),
+                  element_faster_beyond_spread=bool(max(t["element"]) < min(t["assembled"]))))
+    # the wider index table: per-DoF K against the per-node free-slip K on the same lattice
+    fs = domain(nelem, ngl, {"custom-func": {"name": "taylor_green3d"}})
+    ops = {"per_dof": mats["element"].K, "per_node": Mat.createKLEElement(fs.mesh, "K")}
+    x = ops["per_dof"].createVecRight()
+    x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+    y = ops["per_dof"].createVecLeft()
+    t = time_legs(ops, x, y)
+    for label, A in ops.items():
+        emit(dict(base, leg="product_K_dof_vs_node", operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                  reps=a.reps, us=spread(t[label])))
+    emit(dict(base, leg="ratio_K_dof_vs_node", per_dof_over_per_node=statistics.median(t["per_dof"]) /
+              statistics.median(t["per_node"]),
+              differ_beyond_spread=bool(max(t["per_node"]) < min(t["per_dof"]) or max(t["per_dof"]) < min(t["per_node"]))))
+    del ops, fs
+    # one solveFS + solve with nothing of the KLE system assembled
+    mat = mats["element"]
+    sol = pa.KleSolver()
+    sol.setMat(mat)
+    sol.setUp()
+    vort = mat.Rw.createVecRight()
+    vort.setArray(np.random.default_rng(3).uniform(-1, 1, vort.getLocalSize()))
+    vel = sol.getSolution()
+    dom.applyBoundaryConditions(vel, "velocity", 0.0, 0.02)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    sol.solveFS(vort)
+    ctx.synchronize()
+    t1 = time.perf_counter()
+    sol.solve(vort)
+    ctx.synchronize()
+    t2 = time.perf_counter()
+    emit(dict(base, leg="solve_ns", nsType="element", ksp="cg + jacobi", rtol=1e-10,
+              solveFS={"wall_ms": 1e3 * (t1 - t0), "iterations": sol.solverFS.getIterationNumber(),
+                       "reason": sol.solverFS.getConvergedReason(), "operator": mat.getKplusKfs().spmvKernel()},
+              solve={"wall_ms": 1e3 * (t2 - t1), "iterations": sol.getKSP().getIterationNumber(),
+                     "reason": sol.getKSP().getConvergedReason(), "operator": mat.K.spmvKernel()},
+              finite=bool(np.all(np.isfinite(vel.getArray())))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", nargs="+", default=["20,16,16:5", "8,8,6:7"], help="nelem:ngl")
@@ -549,11 +694,16 @@ def main():
                     help="the collocation-operator legs: build, products and the evalRHS chain per opType")
     ap.add_argument("--config4", action="store_true",
                     help="with --operators: one evalRHS at [18,18,18] ngl 7 with nothing assembled, instead of the legs")
+    ap.add_argument("--noslip", action="store_true",
+                    help="the matrix-free no-slip legs on a six-wall lid-driven box at the first mesh")
+    ap.add_argument("--fallback-meshes", nargs="*", default=["16,12,12:5", "12,10,10:5", "8,8,6:5"],
+                    help="with --noslip: tried in order where the assembled no-slip set cannot be built")
     ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree, "
-                                                "operators.jsonl with --operators)")
+                                                "operators.jsonl with --operators, noslip.jsonl with --noslip)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "elem", "operators.jsonl" if a.operators else
+        a.out = os.path.join(ROOT, "profiles", "elem", "noslip.jsonl" if a.noslip else
+                             "operators.jsonl" if a.operators else
                              "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
     import numpy as np
 
@@ -569,6 +719,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.noslip:
+        noslip(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     if a.operators:
         (config4 if a.config4 else operators)(a, pa, np, hip, ctx, emit)
         fout.close()
