@@ -507,6 +507,16 @@ int kle_mat_create_aij_csr(kle_ctx *ctx, int64_t m, int64_t n, const int64_t *in
 int kle_mat_set_values(kle_mat *A, int32_t nr, const int64_t *rows, int32_t nc,
                        const int64_t *cols, const double *v_rowmajor, int addv);
 int kle_mat_assemble(kle_mat *A);
+/* State of a generic AIJ matrix, as PETSc's: between creation and the first
+ * kle_mat_assemble, and again between a kle_mat_set_values on the assembled
+ * matrix and the next kle_mat_assemble, the matrix is not assembled.  In both
+ * states kle_mat_mult, kle_mat_mult_add, kle_mat_get_diagonal, kle_mat_get_row,
+ * kle_mat_get_csr_size, kle_mat_get_csr, kle_mat_duplicate, kle_mat_convert_aij,
+ * kle_mat_diagonal_scale, kle_mat_axpy (either operand), kle_ksp_set_operators,
+ * kle_ksp_set_up and kle_ksp_solve return KLE_ERR_STATE before any device work
+ * and change nothing; kle_mat_assemble then makes the pending values visible
+ * to all of them.  An insertion outside the assembled pattern stays
+ * KLE_ERR_NEWNZ. */
 int kle_mat_destroy(kle_mat *A);
 int kle_mat_get_size(const kle_mat *A, int64_t *m_global, int64_t *n_global);
 int kle_mat_get_ownership_range(const kle_mat *A, int64_t *lo, int64_t *hi);
@@ -527,9 +537,16 @@ typedef struct {
 int kle_mat_get_info(const kle_mat *A, kle_mat_info *info);
 int kle_mat_mult(kle_mat *A, kle_vec *x, kle_vec *y);            /* y = A x */
 int kle_mat_mult_add(kle_mat *A, kle_vec *x, kle_vec *y, kle_vec *z); /* z = y + A x */
+/* A = diag(L) A diag(R), either may be NULL; every node-block shape the
+ * product has a kernel for (3x2 and 2x3 of the 2-D SrT / DivSrT included).
+ * R of a node-block matrix is a mesh vector of its column space. */
 int kle_mat_diagonal_scale(kle_mat *A, const kle_vec *L, const kle_vec *R);
 int kle_mat_get_diagonal(const kle_mat *A, kle_vec *d);
-/* Y += a X where X's pattern is a subset of, or equal to, Y's. */
+/* Y += a X where X's pattern is a subset of, or equal to, Y's.  Node-block
+ * matrices: the same blocks AND the same export rule (DoF mask rule and
+ * classes, diagonal-only Dirichlet rows) -- anything else is KLE_ERR_SUP, so
+ * that the sum never multiplies by an entry its export does not show
+ * (Mat.__add__ then forms the union-pattern AIJ sum). */
 int kle_mat_axpy(kle_mat *Y, double a, const kle_mat *X);
 int kle_mat_duplicate(const kle_mat *A, int copy_values, kle_mat **out);
 /* Scalar CSR of the owned rows with GLOBAL column ids, PETSc pattern. */

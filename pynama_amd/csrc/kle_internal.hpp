@@ -332,6 +332,9 @@ int halo_exchange(kle_ctx *ctx, double *base, int64_t ghost_lo, int64_t n_local,
                   const HaloPlan *plan = nullptr);
 // y = A x; istate (may be null): no-op once the Krylov reason word is set
 int spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+// 0, or KLE_ERR_STATE for a scalar AIJ matrix that is not assembled or holds
+// setValues not yet assembled: called before its device arrays are read
+int aij_ready(const kle_mat *A, const char *what);
 // y = A x and, where the SpMV can form them, the per-workgroup partials of
 // (y, x) in dpart: *nparts of them (0: none written -- the caller forms them)
 int spmv_dot(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart, int *nparts);

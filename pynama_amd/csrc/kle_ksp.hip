@@ -1958,6 +1958,7 @@ int kle_ksp_set_operators(kle_ksp *k, kle_mat *A)
     KLE_ARG(k && A, "null arg");
     if (A->kind == 2 && A->colloc)
         return fail(KLE_ERR_SUP, "KSP: an element-wise collocation operator is no system matrix");
+    KLE_TRY(aij_ready(A, "KSP operator"));
     KLE_ARG(A->m_global == A->n_global, "KSP needs a square operator");
     k->A = A;
     k->setup = false;
@@ -1967,6 +1968,7 @@ int kle_ksp_set_operators(kle_ksp *k, kle_mat *A)
 int kle_ksp_set_up(kle_ksp *k)
 {
     KLE_ARG(k && k->A, "operators not set");
+    KLE_TRY(aij_ready(k->A, "KSP operator"));  // (setValues after setOperators: before any product, set up or not)
     if (k->setup) return 0;
     if (k->pc == "lu") KLE_NO_ELEM(k->A, "PC lu");
     free_work(k);

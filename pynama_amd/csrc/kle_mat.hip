@@ -910,6 +910,20 @@ static int aij_upload(kle_mat *A)
     return 0;
 }
 
+// A scalar AIJ matrix may be read (d_a*, h_ptr) only between assemble() and
+// the next setValues: before the first assemble() the device arrays do not
+// exist, after a setValues the device values are stale and the host mirror
+// holds what the next assemble() uploads.  PETSc refuses both states
+// (PETSC_ERR_ARG_WRONGSTATE); so does every entry point below, before any
+// copy or launch.  Other kinds: always readable.
+int aij_ready(const kle_mat *A, const char *what)
+{
+    if (A->kind != 1) return 0;
+    if (!A->assembled) return fail(KLE_ERR_STATE, "%s: matrix not assembled", what);
+    if (A->dirty) return fail(KLE_ERR_STATE, "%s: setValues since the last assemble()", what);
+    return 0;
+}
+
 }  // namespace kle
 
 using namespace kle;
@@ -1151,7 +1165,7 @@ int kle_mat_get_local_nnz(const kle_mat *A, int64_t *nnz)
 int kle_mat_mult(kle_mat *A, kle_vec *x, kle_vec *y)
 {
     KLE_ARG(A && x && y, "null arg");
-    if (A->kind == 1 && !A->assembled) return fail(KLE_ERR_STATE, "matrix not assembled");
+    KLE_TRY(aij_ready(A, "mult"));
     KLE_TRY(check_mult_layout(A, x, y));
     return spmv(A, x, y, nullptr);
 }
@@ -1159,6 +1173,7 @@ int kle_mat_mult(kle_mat *A, kle_vec *x, kle_vec *y)
 int kle_mat_mult_add(kle_mat *A, kle_vec *x, kle_vec *y, kle_vec *z)
 {
     KLE_ARG(A && x && y && z, "null arg");
+    KLE_TRY(aij_ready(A, "multAdd"));
     kle_vec *t;
     KLE_TRY(kle_vec_duplicate(z, &t));
     KLE_TRY(kle_mat_mult(A, x, t));
@@ -1172,6 +1187,7 @@ int kle_mat_diagonal_scale(kle_mat *A, const kle_vec *L, const kle_vec *Rv)
 {
     KLE_ARG(A, "null mat");
     KLE_NO_ELEM(A, "diagonalScale");
+    KLE_TRY(aij_ready(A, "diagonalScale"));
     sym_drop(A);  // the symmetric copy no longer describes the values
     kle_ctx *c = A->ctx;
     if (L && L->n_local != A->m_local) return fail(KLE_ERR_SIZ, "left scaling vector size mismatch");
@@ -1192,7 +1208,8 @@ int kle_mat_diagonal_scale(kle_mat *A, const kle_vec *L, const kle_vec *Rv)
                            L ? L->d : nullptr, rx);                                                        \
     else
         SC_CASE(3, 3) SC_CASE(2, 2) SC_CASE(2, 1) SC_CASE(1, 2) SC_CASE(3, 1) SC_CASE(1, 3) SC_CASE(6, 3)
-        SC_CASE(3, 6) SC_CASE(1, 1) return fail(KLE_ERR_SUP, "no scale kernel for %dx%d", A->R, A->C);
+        SC_CASE(3, 6) SC_CASE(3, 2) SC_CASE(2, 3) SC_CASE(1, 1)
+        return fail(KLE_ERR_SUP, "no scale kernel for %dx%d", A->R, A->C);
 #undef SC_CASE
     } else {
         if (Rv && Rv->n_local != A->n_local) return fail(KLE_ERR_SIZ, "right scaling vector size mismatch");
@@ -1209,6 +1226,7 @@ int kle_mat_diagonal_scale(kle_mat *A, const kle_vec *L, const kle_vec *Rv)
 int kle_mat_get_diagonal(const kle_mat *A, kle_vec *d)
 {
     KLE_ARG(A && d, "null arg");
+    KLE_TRY(aij_ready(A, "getDiagonal"));
     KLE_ARG(d->n_local == A->m_local, "diagonal vector size mismatch");
     if (A->kind == 2 && A->colloc)
         return fail(KLE_ERR_SUP, "getDiagonal: an element-wise collocation operator holds no diagonal");
@@ -1238,9 +1256,10 @@ int kle_mat_get_csr_size(const kle_mat *A, int64_t *m_local, int64_t *nnz)
 {
     KLE_ARG(A && m_local && nnz, "null arg");
     KLE_NO_ELEM(A, "CSR export");
+    KLE_TRY(aij_ready(A, "CSR export"));
     *m_local = A->m_local;
     if (A->kind == 1) {
-        *nnz = A->assembled ? A->nnz : 0;
+        *nnz = A->nnz;
         return 0;
     }
     if (A->mask_rule != MASK_NONE) {
@@ -1270,12 +1289,12 @@ int kle_mat_get_row(const kle_mat *A, int64_t row, int64_t *ncols, int64_t *cols
 {
     KLE_ARG(A && ncols, "null arg");
     KLE_NO_ELEM(A, "getRow");
+    KLE_TRY(aij_ready(A, "getRow"));
     KLE_ARG(row >= A->row_lo && row < A->row_lo + A->m_local, "row %lld not owned", (long long)row);
     const int64_t lr = row - A->row_lo;
     std::vector<int64_t> c;
     std::vector<double> v;
     if (A->kind == 1) {
-        KLE_ARG(A->assembled, "matrix not assembled");
         const int64_t b = A->h_ptr[lr], e = A->h_ptr[lr + 1];
         c.assign(A->h_col.begin() + b, A->h_col.begin() + e);
         v.resize(e - b);
@@ -1321,8 +1340,9 @@ int kle_mat_get_csr(const kle_mat *A, int64_t *indptr, int64_t *indices, double 
 {
     KLE_ARG(A && indptr && indices && data, "null arg");
     KLE_NO_ELEM(A, "CSR export");
+    KLE_TRY(aij_ready(A, "CSR export"));
     if (A->kind == 1) {
-        KLE_HIP(hipMemcpy(data, A->d_aval, sizeof(double) * A->nnz, hipMemcpyDeviceToHost));
+        if (A->nnz) KLE_HIP(hipMemcpy(data, A->d_aval, sizeof(double) * A->nnz, hipMemcpyDeviceToHost));
         memcpy(indptr, A->h_ptr.data(), sizeof(int64_t) * (A->m_local + 1));
         memcpy(indices, A->h_col.data(), sizeof(int64_t) * A->nnz);
         return 0;
@@ -1359,6 +1379,7 @@ int kle_mat_convert_aij(const kle_mat *A, kle_mat **out)
 {
     KLE_ARG(A && out, "null arg");
     KLE_NO_ELEM(A, "convert");
+    KLE_TRY(aij_ready(A, "convert"));
     KLE_ARG(A->ctx->nranks == 1, "convert_aij is single-rank");
     int64_t m, z;
     KLE_TRY(kle_mat_get_csr_size(A, &m, &z));
@@ -1382,16 +1403,24 @@ int kle_mat_axpy(kle_mat *Y, double a, const kle_mat *X)
     KLE_ARG(Y && X, "null arg");
     KLE_NO_ELEM(Y, "axpy");
     KLE_NO_ELEM(X, "axpy");
+    KLE_TRY(aij_ready(Y, "axpy (Y)"));
+    KLE_TRY(aij_ready(X, "axpy (X)"));
     sym_drop(Y);
     KLE_ARG(Y->kind == X->kind && Y->m_local == X->m_local && Y->n_local == X->n_local, "layout mismatch");
     kle_ctx *c = Y->ctx;
     if (Y->kind == 0) {
-        KLE_ARG(Y->R == X->R && Y->C == X->C && Y->nblocks == X->nblocks, "axpy needs the same pattern");
+        KLE_ARG(Y->R == X->R && Y->C == X->C, "axpy needs the same block shape");
+        if (Y->nblocks != X->nblocks) return fail(KLE_ERR_SUP, "axpy needs the same pattern");
         NBHost hy, hx;
         KLE_TRY(nb_download(Y, hy));
         KLE_TRY(nb_download(X, hx));
         if (hy.rp != hx.rp || hy.bc != hx.bc || hy.cnt != hx.cnt || hy.vp != hx.vp || Y->vlayout != X->vlayout)
             return fail(KLE_ERR_SUP, "axpy needs the same pattern");
+        // the same blocks under different export rules (DoF masks, diagonal-only
+        // Dirichlet rows): X's entries would land where Y's export shows none
+        // and the sum would multiply by more than it exports
+        if (Y->mask_rule != X->mask_rule || Y->dof_cls != X->dof_cls || Y->diag_only_row != X->diag_only_row)
+            return fail(KLE_ERR_SUP, "axpy needs the same pattern (the export rules differ)");
         const int64_t n = Y->nvals;
         hipLaunchKernelGGL(k_axpy_same, dim3(grid_for(n, 256, 2048)), dim3(256), 0, c->stream, n, a, X->d_val, Y->d_val);
         KLE_HIP(hipGetLastError());
@@ -1422,6 +1451,7 @@ int kle_mat_duplicate(const kle_mat *A, int copy_values, kle_mat **out)
 {
     KLE_ARG(A && out, "null arg");
     KLE_NO_ELEM(A, "duplicate");
+    KLE_TRY(aij_ready(A, "duplicate"));
     kle_mat *B = new kle_mat(*A);
     B->d_rowcnt = nullptr;
     B->d_rowbox = nullptr;
