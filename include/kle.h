@@ -39,6 +39,7 @@ enum {
     KLE_OK = 0,
     KLE_ERR_ARG = 62,        /* PETSC_ERR_ARG_WRONG          */
     KLE_ERR_SIZ = 60,        /* PETSC_ERR_ARG_SIZ            */
+    KLE_ERR_IDN = 61,        /* PETSC_ERR_ARG_IDN: an output vector that is also an input */
     KLE_ERR_OUTOFRANGE = 63, /* PETSC_ERR_ARG_OUTOFRANGE     */
     KLE_ERR_MEM = 55,        /* PETSC_ERR_MEM                */
     KLE_ERR_SUP = 56,        /* PETSC_ERR_SUP (not supported) */
@@ -310,6 +311,9 @@ int kle_vec_destroy(kle_vec *v);
 int kle_vec_get_sizes(const kle_vec *v, int64_t *n_local, int64_t *n_global);
 int kle_vec_get_ownership_range(const kle_vec *v, int64_t *lo, int64_t *hi);
 int kle_vec_set(kle_vec *v, double alpha);
+/* Aliasing: axpy, aypx and waxpy return KLE_ERR_IDN, with the vectors
+ * unchanged, when the output is also an input (VecAXPY, VecAYPX, VecWAXPY);
+ * pointwise_mult takes w == x, w == y and w == x == y (VecPointwiseMult). */
 int kle_vec_copy(const kle_vec *x, kle_vec *y);                 /* y = x          */
 int kle_vec_axpy(kle_vec *y, double alpha, const kle_vec *x);   /* y += a x       */
 int kle_vec_aypx(kle_vec *y, double beta, const kle_vec *x);    /* y = x + b y    */
@@ -320,11 +324,23 @@ int kle_vec_pointwise_mult(kle_vec *w, const kle_vec *x, const kle_vec *y);
  * (2-D) or xx,xy,yy,yz,zz,zx (3-D): BaseProblem.computeVtensV
  * (base_problem.py:138-154). */
 int kle_vec_tensor_square(const kle_vec *v, int dim, kle_vec *out);
+/* 1 / v_i; an entry that compares equal to 0 stays as it is (VecReciprocal). */
 int kle_vec_reciprocal(kle_vec *v);
 int kle_vec_dot(const kle_vec *x, const kle_vec *y, double *out);
+/* The 2-norm to a few roundings whenever it is representable: sqrt of the sum
+ * of squares while that sum is finite and at least 2^-969 (no extra launch or
+ * synchronisation on that path), else a max-abs pass and the sum of squares of
+ * the entries scaled by a power of two (entries near 2^+-600 do not give inf
+ * or 0).  NaN for a NaN entry, inf for an infinite one, 0.0 for all zeros. */
 int kle_vec_norm2(const kle_vec *x, double *out);
-/* Host <-> device.  Indices are GLOBAL; only owned entries may be set.
- * addv: 0 INSERT_VALUES, 1 ADD_VALUES (applied in index order). */
+/* Host <-> device.  Indices are GLOBAL; only owned entries may be set
+ * (KLE_ERR_OUTOFRANGE otherwise, before anything is written).
+ * addv: 0 INSERT_VALUES (an index given more than once takes the last value
+ * given), 1 ADD_VALUES (applied in list order).
+ * get_values also reads the ghost entries of a mesh vector, as they stand
+ * since the last ghost update: on slab partitions the neighbouring index
+ * ranges, on graph partitions the entries of the ghost nodes
+ * (kle_mesh_get_ext_gids); any other index is KLE_ERR_OUTOFRANGE. */
 int kle_vec_set_values(kle_vec *v, int64_t n, const int64_t *idx, const double *vals, int addv);
 int kle_vec_get_values(const kle_vec *v, int64_t n, const int64_t *idx, double *vals);
 int kle_vec_get_array(const kle_vec *v, double *host_local);     /* owned part */

@@ -190,8 +190,8 @@ __global__ void k_vtensv(int64_t nodes, const double *__restrict__ v, double *__
     }
 }
 
-__global__ void k_pmult(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
-                        double *__restrict__ w)
+// w may be x, y or both (VecPointwiseMult allows it): no __restrict__ here
+__global__ void k_pmult(int64_t n, const double *x, const double *y, double *w)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
@@ -200,10 +200,12 @@ __global__ void k_pmult(int64_t n, const double *__restrict__ x, const double *_
 
 __global__ void k_recip(int64_t n, double *__restrict__ y)
 {
-    // VecReciprocal: zero entries stay zero (PETSc semantics)
+    // VecReciprocal: an entry that compares equal to 0 stays as it is (-0.0 stays -0.0)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        y[i] = y[i] != 0.0 ? 1.0 / y[i] : 0.0;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = y[i];
+        y[i] = v != 0.0 ? 1.0 / v : v;
+    }
 }
 
 __global__ void k_dot_partial(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
@@ -214,6 +216,44 @@ __global__ void k_dot_partial(int64_t n, const double *__restrict__ x, const dou
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
         s += x[i] * y[i];
+    s = block_sum(s, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The scaled 2-norm's two passes (kle_vec_norm2, taken only when the plain sum
+// of squares overflowed, vanished or fell among the subnormals).  Pass 1: each
+// block's max |x_i| (fmax drops NaNs; the caller has returned NaN before).
+__global__ void k_absmax_partial(int64_t n, const double *__restrict__ x, double *__restrict__ partials)
+{
+    __shared__ double lds[16];
+    double s = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        s = fmax(s, fabs(x[i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s = fmax(s, __shfl_xor(s, o, 64));
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if (lane == 0) lds[w] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < nw; ++i) s = fmax(s, lds[i]);
+        partials[blockIdx.x] = s;
+    }
+}
+
+// Pass 2: sum of (x_i 2^-e)^2 in k_dot_partial's order; the scaling is exact
+// (an entry that it makes subnormal is below 2^-1021 of the largest, and its
+// square is nothing beside 1).
+__global__ void k_sumsq_scaled_partial(int64_t n, const double *__restrict__ x, int e,
+                                       double *__restrict__ partials)
+{
+    __shared__ double lds[16];
+    double s = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double t = ldexp(x[i], -e);
+        s += t * t;
+    }
     s = block_sum(s, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
@@ -1195,6 +1235,7 @@ int kle_vec_create_mesh(kle_ctx *ctx, const kle_mesh *m, int bs, kle_vec **out)
     v->send_lo = m->send_lo_nodes * bs;
     v->send_hi = m->send_hi_nodes * bs;
     v->plan = m->plan;
+    v->ext_gid = m->ext_lookup;
     return 0;
 }
 
@@ -1209,6 +1250,7 @@ int kle_vec_duplicate(const kle_vec *v, kle_vec **out)
     w->send_lo = v->send_lo;
     w->send_hi = v->send_hi;
     w->plan = v->plan;
+    w->ext_gid = v->ext_gid;
     return 0;
 }
 
@@ -1256,6 +1298,14 @@ static int same_layout(const kle_vec *a, const kle_vec *b)
     return 0;
 }
 
+// VecAXPY, VecAYPX and VecWAXPY refuse an output that is also an input
+// (PETSC_ERR_ARG_IDN); their kernels declare every pointer __restrict__.
+static int not_same(const kle_vec *out, const kle_vec *in, const char *what)
+{
+    if (out == in || out->d == in->d) return fail(KLE_ERR_IDN, "%s: the output vector is also an input", what);
+    return 0;
+}
+
 int kle_vec_copy(const kle_vec *x, kle_vec *y)
 {
     KLE_ARG(x && y, "null vec");
@@ -1269,6 +1319,7 @@ int kle_vec_axpy(kle_vec *y, double a, const kle_vec *x)
 {
     KLE_ARG(x && y, "null vec");
     KLE_TRY(same_layout(x, y));
+    KLE_TRY(not_same(y, x, "axpy"));
     hipLaunchKernelGGL(k_axpy, dim3(VGRID(y->n_local)), dim3(VB), 0, y->ctx->stream, y->n_local, a,
                        x->d, y->d);
     KLE_HIP(hipGetLastError());
@@ -1279,6 +1330,7 @@ int kle_vec_aypx(kle_vec *y, double b, const kle_vec *x)
 {
     KLE_ARG(x && y, "null vec");
     KLE_TRY(same_layout(x, y));
+    KLE_TRY(not_same(y, x, "aypx"));
     hipLaunchKernelGGL(k_aypx, dim3(VGRID(y->n_local)), dim3(VB), 0, y->ctx->stream, y->n_local, b,
                        x->d, y->d);
     KLE_HIP(hipGetLastError());
@@ -1290,6 +1342,8 @@ int kle_vec_waxpy(kle_vec *w, double a, const kle_vec *x, const kle_vec *y)
     KLE_ARG(w && x && y, "null vec");
     KLE_TRY(same_layout(x, y));
     KLE_TRY(same_layout(x, w));
+    KLE_TRY(not_same(w, x, "waxpy"));
+    KLE_TRY(not_same(w, y, "waxpy"));
     hipLaunchKernelGGL(k_waxpy, dim3(VGRID(w->n_local)), dim3(VB), 0, w->ctx->stream, w->n_local,
                        a, x->d, y->d, w->d);
     KLE_HIP(hipGetLastError());
@@ -1358,11 +1412,63 @@ int kle_vec_dot(const kle_vec *x, const kle_vec *y, double *out)
     return 0;
 }
 
+// sqrt(sum x_i^2) as long as that sum is finite and normal with room for its
+// terms: nothing is added to that path.  A sum that is inf, 0 or below 2^-969
+// says nothing about the norm (squares overflowed, or fell among the
+// subnormals), so the norm is taken again as 2^e sqrt(sum (x_i 2^-e)^2) with
+// 2^e just above max |x_i| (BLAS nrm2's scaling, exact with a power of two).
 int kle_vec_norm2(const kle_vec *x, double *out)
 {
+    KLE_ARG(x && out, "null arg");
     double d;
     KLE_TRY(kle_vec_dot(x, x, &d));
-    *out = std::sqrt(d);
+    if (d >= 0x1p-969 && d < HUGE_VAL) {
+        *out = std::sqrt(d);
+        return 0;
+    }
+    if (d != d) {  // a NaN entry (squares cannot cancel)
+        *out = d;
+        return 0;
+    }
+    // d is the same on every rank (allreduced), so every rank is here
+    kle_ctx *c = x->ctx;
+    const int g = VGRID(x->n_local);
+    hipLaunchKernelGGL(k_absmax_partial, dim3(g), dim3(VB), 0, c->stream, x->n_local, x->d, c->d_partials);
+    KLE_HIP(hipGetLastError());
+    std::vector<double> part(g);
+    KLE_HIP(hipMemcpyAsync(part.data(), c->d_partials, sizeof(double) * g, hipMemcpyDeviceToHost, c->stream));
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    double mx = 0;
+    for (double v : part) mx = std::max(mx, v);
+    if (c->nranks > 1) {  // max over the ranks: one-hot sum (exact)
+        std::vector<double> h(c->nranks, 0.0);
+        h[c->rank] = mx;
+        double *dm;
+        KLE_HIP(hipMalloc(&dm, sizeof(double) * c->nranks));
+        int rc = 0;
+        if (hipMemcpyAsync(dm, h.data(), sizeof(double) * c->nranks, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            rc = fail(KLE_ERR_DEVICE, "norm: upload of the rank maxima failed");
+        if (!rc) rc = allreduce_sum(c, dm, c->nranks);
+        if (!rc && hipMemcpyAsync(h.data(), dm, sizeof(double) * c->nranks, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = fail(KLE_ERR_DEVICE, "norm: copy of the rank maxima failed");
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(KLE_ERR_DEVICE, "norm: synchronize failed");
+        hipFree(dm);
+        if (rc) return rc;
+        for (double v : h) mx = std::max(mx, v);
+    }
+    if (mx == 0.0 || mx == HUGE_VAL) {  // all zero; an infinite entry
+        *out = mx;
+        return 0;
+    }
+    int e;
+    std::frexp(mx, &e);  // mx = f 2^e, f in [0.5, 1)
+    hipLaunchKernelGGL(k_sumsq_scaled_partial, dim3(g), dim3(VB), 0, c->stream, x->n_local, x->d, e, c->d_partials);
+    KLE_HIP(hipGetLastError());
+    KLE_TRY(reduce_partials(c, c->d_partials, g, 1, c->d_scal + S_TMP0));
+    KLE_TRY(allreduce_sum(c, c->d_scal + S_TMP0, 1));
+    KLE_HIP(hipMemcpyAsync(c->h_scal + S_TMP0, c->d_scal + S_TMP0, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    *out = std::ldexp(std::sqrt(c->h_scal[S_TMP0]), e);
     return 0;
 }
 
@@ -1377,6 +1483,28 @@ int kle_vec_set_values(kle_vec *v, int64_t n, const int64_t *idx, const double *
             return fail(KLE_ERR_OUTOFRANGE, "index %lld not owned ([%lld,%lld))",
                         (long long)idx[i], (long long)v->lo, (long long)(v->lo + v->n_local));
         loc[i] = l;
+    }
+    // INSERT with a repeated index: the last value given wins (VecSetValues).
+    // The scatter takes one thread per entry, so only the last occurrence of
+    // each index is uploaded.
+    std::vector<double> kept;
+    if (!addv) {
+        bool ascending = true;
+        for (int64_t i = 1; i < n && ascending; ++i) ascending = loc[i - 1] < loc[i];
+        if (!ascending) {
+            std::vector<int64_t> ord(n);
+            for (int64_t i = 0; i < n; ++i) ord[i] = i;
+            std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return loc[a] < loc[b]; });
+            std::vector<int64_t> uloc;
+            for (int64_t k = 0; k < n; ++k)
+                if (k + 1 == n || loc[ord[k + 1]] != loc[ord[k]]) {
+                    uloc.push_back(loc[ord[k]]);
+                    kept.push_back(vals[ord[k]]);
+                }
+            loc.swap(uloc);
+            n = (int64_t)loc.size();
+            vals = kept.data();
+        }
     }
     int64_t *di;
     double *dv;
@@ -1401,6 +1529,15 @@ int kle_vec_get_values(const kle_vec *v, int64_t n, const int64_t *idx, double *
     std::vector<int64_t> loc(n);
     for (int64_t i = 0; i < n; ++i) {
         int64_t l = idx[i] - v->lo;
+        if (v->ext_gid && (l < 0 || l >= v->n_local)) {
+            // graph partition: ghost position k holds node ext_gid[k], wherever its index lies
+            const std::vector<int64_t> &eg = *v->ext_gid;
+            const int64_t node = idx[i] >= 0 ? idx[i] / v->bs : -1;
+            auto it = std::lower_bound(eg.begin(), eg.end(), node);
+            if (it == eg.end() || *it != node)
+                return fail(KLE_ERR_OUTOFRANGE, "index %lld is neither owned nor a ghost", (long long)idx[i]);
+            l = (int64_t)(it - eg.begin()) * v->bs + idx[i] % v->bs - v->ghost_lo;
+        }
         if (l < -v->ghost_lo || l >= v->n_local + v->ghost_hi)
             return fail(KLE_ERR_OUTOFRANGE, "index %lld not local", (long long)idx[i]);
         loc[i] = l;

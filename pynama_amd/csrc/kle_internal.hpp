@@ -167,6 +167,9 @@ struct kle_mesh {
     // (empty: pseudo id == global id, the slab layouts)
     kle::PlanPtr plan;
     std::vector<int64_t> ext_gid;
+    // the same list (it ascends), shared with the mesh vectors: kle_vec_get_values
+    // finds a ghost's position by binary search in it (built once per mesh)
+    std::shared_ptr<const std::vector<int64_t>> ext_lookup;
     int64_t to_global(int64_t pseudo) const { return ext_gid.empty() ? pseudo : ext_gid[pseudo - ext_begin]; }
     // global id -> pseudo id, -1 when the node is not in the ext range
     int64_t to_pseudo(int64_t gid) const;
@@ -193,6 +196,9 @@ struct kle_vec {
     int lo_rank = -1, hi_rank = -1;
     int64_t send_lo = 0, send_hi = 0;
     kle::PlanPtr plan;  // general halo (graph partitions); overrides lo/hi ranks
+    // graph partitions: global node of every ext position (ascending), the mesh's; null: the
+    // ghosts are the neighbouring index ranges (slab layouts, plain vectors)
+    std::shared_ptr<const std::vector<int64_t>> ext_gid;
     bool owns = true;
 };
 

@@ -1177,7 +1177,9 @@ int kle_mat_mult_add(kle_mat *A, kle_vec *x, kle_vec *y, kle_vec *z)
     kle_vec *t;
     KLE_TRY(kle_vec_duplicate(z, &t));
     KLE_TRY(kle_mat_mult(A, x, t));
-    KLE_TRY(kle_vec_waxpy(z, 1.0, t, y));
+    // z == y is allowed (MatMultAdd); waxpy refuses an output that is an input
+    if (z == y) KLE_TRY(kle_vec_axpy(z, 1.0, t));
+    else KLE_TRY(kle_vec_waxpy(z, 1.0, t, y));
     KLE_HIP(hipStreamSynchronize(A->ctx->stream));
     kle_vec_destroy(t);
     return 0;

@@ -659,6 +659,7 @@ int kle_mesh_create_unstructured(int dim, int ngl, int64_t nverts, const double 
     m->ext_end = ext_end;
     m->plan = plan;
     m->ext_gid = std::move(ext_gid);
+    if (!m->ext_gid.empty()) m->ext_lookup = std::make_shared<const std::vector<int64_t>>(m->ext_gid);
     if (slab && rank > 0) {
         m->halo_lo_rank = rank - 1;
         m->halo_lo_nodes = nhi[rank - 1];
