@@ -129,7 +129,20 @@ const char *kle_last_error(void);
  * x is in LDS; 0 default), "spmv_sym_align" (read at build: partial slots
  * aligned to 128-B lines; 0 default), "spmv_sym_stpol"
  * (box kernel's partial stores: 0 plain default, 1 nontemporal, 2 sc1, 3 sc0
- * sc1), "spmv_gsym_stpol" (the same for the graph kernel; default 2).
+ * sc1), "spmv_gsym_stpol" (the same for the graph kernel; default 2),
+ * "spmv_brick_compact" (read at build: the brick value stream of a K that
+ * stores every analytically zero entry as +0.0 -- checked on the device when
+ * the storage is built -- holds the other entries alone, 3, 5 or 9 per block;
+ * 1 default, 0 the full blocks.  The product is the same matrix's either
+ * way: the entries left out are exact zeros),
+ * "asm_box_zeros" (read at assembly; an A/B and diagnosis switch, not a
+ * performance knob: the free-slip K of a 3-D kle_mesh_create_box mesh stores
+ * its analytically zero block entries as +0.0 -- entry (a, b), a != b, of the
+ * block between two nodes that share lattice coordinate a or b on a plane
+ * that is not a domain boundary plane; 1 default, 0 the assembly's rounding
+ * noise there, a few 1e-16 of max|K|.  Every other entry, the pattern, Krhs,
+ * Rw, the operators, the no-slip matrices, 2-D and unstructured meshes are
+ * the same bits for both values).
  * Every value gives correct results (the
  * timing probes of the symmetric SpMV exist only in the tools/ probe build,
  * `make -C pynama_amd/csrc probe`). */
@@ -620,6 +633,11 @@ int kle_mat_get_symmetric(const kle_mat *A, int *on);
  * (tests/test_gpu_fullsize.py). */
 int kle_mat_move_values(kle_mat *A, long long shift, int fresh);
 int kle_mat_get_sym_bricks(const kle_mat *A, int *nbricks, int *dims, double *entries_per_row, double *model_us);
+/* Whether the bricks' value stream is the compact one (tuning
+ * "spmv_brick_compact": a K whose analytically zero entries, "asm_box_zeros",
+ * are all stored as +0.0 streams the other entries alone) and how many entries
+ * it leaves out; 0, 0 otherwise. */
+int kle_mat_get_brick_compact(const kle_mat *A, int *compact, long long *dropped_entries);
 /* N > 1: run the rows that read no ghost entry while the halo exchange is in
  * flight on a second stream (default on). */
 int kle_mat_set_halo_overlap(kle_mat *A, int on);

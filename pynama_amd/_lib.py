@@ -155,6 +155,7 @@ _SIGS = {
     "kle_mat_is_structured": [vp, C.POINTER(C.c_int)],
     "kle_mat_set_symmetric": [vp, C.c_int],
     "kle_mat_get_symmetric": [vp, C.POINTER(C.c_int)],
+    "kle_mat_get_brick_compact": [vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)],
     "kle_mat_get_sym_bricks": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)],
     "kle_get_nb_pad": [],

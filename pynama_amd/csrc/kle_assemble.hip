@@ -525,14 +525,20 @@ __device__ __forceinline__ double sym_elem_entry(const double *__restrict__ Ee, 
     return Ee[((int64_t)lo * ne + hi) * (R * C) + a * C + b];
 }
 
+// (the analytic zeros of a box mesh's K: defined beside the row boxes below)
+__host__ __device__ inline bool box_zero_entry(const int64_t ci[3], const int64_t cj[3], const int64_t L[3], int a,
+                                               int b);
+
 // MODE 0: K (free cols, +K_e), 1: Krhs (Dirichlet cols, -K_e), 2: Rw (+Rw_e)
+// zrule (MODE 0, 3 x 3 blocks): the entries under box_zero_entry are stored
+// as +0.0 (tuning asm_box_zeros)
 template <int R, int C, int MODE>
 __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const int *__restrict__ rowptr,
                                                 const int *__restrict__ rowcnt, const int64_t *__restrict__ vptr,
                                                 int lay, const int *__restrict__ bcol,
                                                 const uint8_t *__restrict__ dir,
                                                 const double *__restrict__ Eblk, double *__restrict__ val,
-                                                int64_t eb0, int64_t eb1, int accum)
+                                                int64_t eb0, int64_t eb1, int accum, int zrule)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -599,6 +605,16 @@ __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const 
                         for (int t = 0; t < R * C; ++t) acc[t] += (MODE == 1) ? -blk[t] : blk[t];
                     }
                 }
+        // (every batch's store: a later batch continues from +0.0 and ends at it)
+        if constexpr (MODE == 0 && R == 3 && C == 3) {
+            if (zrule) {
+#pragma unroll
+                for (int a = 0; a < R; ++a)
+#pragma unroll
+                    for (int b = 0; b < C; ++b)
+                        if (box_zero_entry(ci, cj, M.L, a, b)) acc[a * C + b] = 0.0;
+            }
+        }
 #pragma unroll
         for (int a = 0; a < R; ++a)
 #pragma unroll
@@ -710,6 +726,26 @@ __device__ __forceinline__ bool pat_keep(int which, bool di, bool dj)
     case 5: return dj;
     default: return true;  // 2, 3, 6
     }
+}
+
+// The analytic zeros of the free-slip K of an axis-aligned 3-D box mesh: in
+// the block between lattice nodes ci and cj (global lattice coordinates, L
+// the global lattice: a z slab's end planes are not boundary planes), entry
+// (a, b), a != b, is zero when the nodes share coordinate a or coordinate b
+// and that shared plane is not a plane of the domain boundary -- there the
+// element integrals cancel, between the two elements on either side of an
+// element face and inside one element alike; on a boundary plane the
+// one-sided endpoint terms remain.  Symmetric in (ci, a) <-> (cj, b), so
+// K = K^T stays bit for bit.  The only place that decides the rule
+// (k_gather, tuning asm_box_zeros; tests/test_box_zero_rule.py states it
+// again on the CPU oracle's K).
+__host__ __device__ inline bool box_zero_entry(const int64_t ci[3], const int64_t cj[3], const int64_t L[3], int a,
+                                               int b)
+{
+    if (a == b) return false;
+    const bool sa = ci[a] == cj[a] && ci[a] > 0 && ci[a] < L[a] - 1;
+    const bool sb = ci[b] == cj[b] && ci[b] > 0 && ci[b] < L[b] - 1;
+    return sa || sb;
 }
 
 // neighbour box of node row gi (kle_mesh.cpp nbr_range); returns false for the
@@ -1617,7 +1653,7 @@ static void launch_gather(kle_ctx *ctx, const MeshDev &M, kle_mat *A, const uint
     const int64_t threads = A->nrows * 64;
     hipLaunchKernelGGL((k_gather<R, C, MODE>), dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, M,
                        A->nrows, A->d_rowptr, A->d_rowcnt, A->d_vptr, A->vlayout, A->d_bcol, dir, E, A->d_val,
-                       eb0, eb1, accum);
+                       eb0, eb1, accum, (MODE == 0 && M.dim == 3 && g_tune.asm_box_zeros) ? 1 : 0);
 }
 
 // ------------------------------------------------------- unstructured

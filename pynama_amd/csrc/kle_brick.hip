@@ -46,6 +46,7 @@ using cint = __attribute__((address_space(4))) const int;
 struct BRow {
     const double *v;
     int bnx, bnxy, k0, mu, rb0, ir;
+    int dbb;  // (compact stream: the row's position in its box and its boundary bits, kle_brick.hpp)
 };
 
 // an issued item, packed in five words (SGPRs are the kernel's scarce
@@ -74,7 +75,19 @@ constexpr int BI_NEWP = 1024;  // (sf: the item starts row P -- its x into the r
 // region's transposed sums, each times the x it is added at (the gather adds
 // every one of them to exactly one entry of A x), so the update's prologue
 // has (A x, x) before any row is gathered (kle_ksp.hip k_sr_iter_g)
-template <int WV, bool FF = true, bool DOT = false>
+// CP: the compact value stream (kle_brick.hpp brick_drop_bits; the pack:
+// kle_sym.hip k_brick_pack).  Items, units, the shared tail item, one item in
+// flight and the fixed vmcnt(9) are as without it; only where a lane's nine
+// loads point differs.  Per item and per row part (P's lanes, Q's lanes) the
+// values lie slot-major and compacted: slot t holds the kept lanes' values
+// in lane order, one slot after another.  A lane's place in slot t is the
+// count of kept lanes of its part below it (ballot, mbcnt), the slot's base
+// the running sum of the part's counts, the part's base a wave-uniform
+// running offset along the row's passes (a unit's second row: its last
+// partial pass first, as the shared item reads it before the full passes).
+// A lane whose slot is left out loads its part's first value (a line an
+// active lane of the same load reads) and takes 0.0 after the wait.
+template <int WV, bool FF = true, bool DOT = false, bool CP = false>
 __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly, int Lz, int zo, int hp, int rstride,
                                                                  const BrickDesc *__restrict__ bd,
                                                                  const int2 *__restrict__ rowd,
@@ -179,7 +192,9 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // bnx, bny, bnz: 4 bits each) + the low byte of its region index; value
     // offset / 16 doubles (23 bits) + the high byte
     auto row_setup = [&](int r, int dw, int vw, BRow &R) {
-        const int dbx = dw & 15, dby = (dw >> 4) & 15, dbz = (dw >> 8) & 15;
+        constexpr int DM = CP ? 7 : 15;
+        const int dbx = dw & DM, dby = (dw >> 4) & DM, dbz = (dw >> 8) & DM;
+        R.dbb = dw & 0xFFF;
         R.bnx = (dw >> 12) & 15;
         const int bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
         R.bnxy = R.bnx * bny;
@@ -193,28 +208,66 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // the others from row Q's blocks kbQ + lane - s (Q's values follow P's);
     // lanes past a row's end re-read its last block (their results go
     // nowhere) -- and each block's region index
-    auto load_v = [&](const BRow &P, const BRow &Q, int kbP, int kbQ, int s, double *vv, int &rr) {
+    // (CP: oP / oQ the parts' first doubles in their rows' streams; zP / zQ
+    // the doubles the parts hold; rr then carries the lane's left-out pairs
+    // in bits 16..18)
+    auto load_v = [&](const BRow &P, const BRow &Q, int kbP, int kbQ, int s, double *vv, int &rr, int oP, int oQ,
+                      int &zP, int &zQ) {
         const bool q = lane >= s;
         const int mu = q ? Q.mu : P.mu;
-        const int kk = min(q ? kbQ + lane - s : kbP + lane, mu - 1);
-        const int q16 = mu & ~15;
-        const bool ch = kk < q16;
-        const int o0 = ch ? (kk >> 4) * 144 + (kk & 15) : q16 * 9 + (kk - q16);
-        const int st = ch ? 16 : mu - q16;
+        const int kraw = q ? kbQ + lane - s : kbP + lane;
+        const int kk = min(kraw, mu - 1);
         const unsigned bo = q ? (unsigned)(Q.v - P.v) * 8u : 0u;
-        unsigned o[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) o[t] = bo + (unsigned)(o0 + t * st) * 8u;
-        // (the base is wave-uniform; said so, as the loads take it in SGPRs)
-        const unsigned long long pb = (unsigned long long)P.v;
-        const unsigned phi = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb >> 32));
-        const unsigned plo = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb & 0xffffffffull));
-        sym_ld9(vv, reinterpret_cast<const double *>(((unsigned long long)phi << 32) | plo), o);
         const int k = (q ? Q.k0 : P.k0) + kk;
         const int bnxy = q ? Q.bnxy : P.bnxy, bnx = q ? Q.bnx : P.bnx;
         const int kz = sym_div(k, bnxy, __builtin_amdgcn_rcpf((float)bnxy)), rem = k - kz * bnxy;
         const int ky = sym_div(rem, bnx, __builtin_amdgcn_rcpf((float)bnx)), kx = rem - ky * bnx;
         rr = (q ? Q.rb0 : P.rb0) + kx + RX * (ky + RY * kz);
+        unsigned o[9];
+        if constexpr (!CP) {
+            const int q16 = mu & ~15;
+            const bool ch = kk < q16;
+            const int o0 = ch ? (kk >> 4) * 144 + (kk & 15) : q16 * 9 + (kk - q16);
+            const int st = ch ? 16 : mu - q16;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) o[t] = bo + (unsigned)(o0 + t * st) * 8u;
+            zP = zQ = 0;
+        } else {
+            const bool act = kraw < mu;
+            const int db = brick_drop_bits(q ? Q.dbb : P.dbb, kx, ky, kz);
+            const bool kp[3] = {act && !(db & 1), act && !(db & 2), act && !(db & 4)};
+            // the kept lanes of the diagonal slots and of the three pairs
+            const unsigned long long mP = s >= 64 ? ~0ull : (1ull << s) - 1ull;
+            const unsigned long long bl[4] = {__ballot(act), __ballot(kp[0]), __ballot(kp[1]), __ballot(kp[2])};
+            int nP[4], nQ[4], n[4], c[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                nP[g] = __popcll(bl[g] & mP);
+                nQ[g] = __popcll(bl[g] & ~mP);
+                n[g] = q ? nQ[g] : nP[g];
+                // (kept lanes of the lane's part below it)
+                c[g] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl[g] >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo((unsigned)bl[g], 0u)) -
+                       (q ? nP[g] : 0);
+            }
+            zP = 3 * nP[0] + 2 * (nP[1] + nP[2] + nP[3]);
+            zQ = 3 * nQ[0] + 2 * (nQ[1] + nQ[2] + nQ[3]);
+            const unsigned pb0 = bo + (unsigned)(q ? oQ : oP) * 8u;
+            int sb = 0;  // (the slot's base in the part)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int g = brick_slot_pair(t) + 1;
+                const bool keep = g == 0 ? act : kp[g - 1];
+                o[t] = keep ? pb0 + (unsigned)(sb + c[g]) * 8u : pb0;
+                sb += n[g];
+            }
+            rr |= db << 16;
+        }
+        // (the base is wave-uniform; said so, as the loads take it in SGPRs)
+        const unsigned long long pb = (unsigned long long)P.v;
+        const unsigned phi = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb >> 32));
+        const unsigned plo = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb & 0xffffffffull));
+        sym_ld9(vv, reinterpret_cast<const double *>(((unsigned long long)phi << 32) | plo), o);
     };
     // 1. units from an LDS counter; each wave's first D + 2 static (w, w + WV,
     // ...: the counter starts past them -- as many as the D items issued
@@ -240,6 +293,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     BRow A, B;
     bool hasB = false, idone = w >= NU;
     int ph = 0, ki = 0, aend = 0, bend = 0;
+    int oa = 0, ob = 0;  // (CP: the cursor's place in A's and in B's stream, doubles)
     auto unit_setup = [&](int u, int d0, int d1, int d2, int d3) {
         row_setup(2 * u, d0, d1, A);
         hasB = (d3 & BRICK_ROW_NULL) == 0;
@@ -249,6 +303,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         bend = hasB ? (B.mu & ~63) : 0;
         ph = aend > 0 ? 0 : 1;
         ki = 0;
+        oa = ob = 0;
     };
     if (!idone) {
         unit_setup(w, rdesc[4 * w], rdesc[4 * w + 1], rdesc[4 * w + 2], rdesc[4 * w + 3]);
@@ -259,6 +314,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         A.bnx = A.bnxy = 1;
         A.rb0 = 0;
         A.ir = 0;
+        A.dbb = 0;
         B = A;
     }
 #ifdef KLE_PROBE_BUILD
@@ -277,26 +333,30 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // the item at the cursor: its loads into vn, its record; the cursor then
     // moves on (past the last unit it stays, re-reading the last item)
     auto issue = [&](double *vn, int &rn, BItem &itn) {
+        int zp, zq;
         if (idone) {  // (a re-read of A's first pass: cache hits, the results go nowhere)
-            load_v(A, A, 0, 0, 64, vn, rn);
+            load_v(A, A, 0, 0, 64, vn, rn, 0, 0, zp, zq);
             itn.ok = 0;
             return;
         }
         if (ph == 0) {  // A's passes
-            load_v(A, A, ki, 0, 64, vn, rn);
+            load_v(A, A, ki, 0, 64, vn, rn, oa, 0, zp, zq);
+            oa += zp;
             itn = bitem(64, A.mu, A.mu, A.ir, A.ir, ki, 0, !hasB && ki + 64 >= A.mu, 0);
             if (ki == 0) itn.sf |= BI_NEWP;
             ki += 64;
             if (ki >= aend) ph = hasB ? 1 : 3;
         } else if (ph == 1) {  // A's and B's last partial passes
             const int s = A.mu - aend;
-            load_v(A, B, aend, bend, s, vn, rn);
+            load_v(A, B, aend, bend, s, vn, rn, oa, 0, zp, zq);  // (B's last partial pass opens its stream)
+            ob = zq;
             itn = bitem(s, A.mu, B.mu, A.ir, B.ir, aend, bend, 1, bend == 0);
             if (aend == 0) itn.sf |= BI_NEWP;
             ki = 0;
             ph = bend > 0 ? 2 : 3;
         } else {  // B's full passes
-            load_v(B, B, ki, 0, 64, vn, rn);
+            load_v(B, B, ki, 0, 64, vn, rn, ob, 0, zp, zq);
+            ob += zp;
             itn = bitem(64, B.mu, B.mu, B.ir, B.ir, ki, 0, ki + 64 >= bend, 0);
             ki += 64;
             if (ki >= bend) ph = 3;
@@ -429,7 +489,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         };
         // one step: issue the next item into vn, wait for vv (the D newer
         // items stay in flight), sum it
-        auto step = [&](double *vv, const int rr, const BItem &it, double *vn, int &rn, BItem &itn) {
+        auto step = [&](double *vv, const int rrk, const BItem &it, double *vn, int &rn, BItem &itn) {
+            const int rr = CP ? rrk & 0xFFFF : rrk;
             issue(vn, rn, itn);
             if (!it.ok) return false;
             const int is = it.sf & 255, irP = it.ir & 0xFFFF, irQ = (int)((unsigned)it.ir >> 16);
@@ -456,6 +517,18 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
             }
             const double xj0 = xl[rr], xj1 = xl[RN + rr], xj2 = xl[2 * RN + rr];
             sym_wait9<9 * D>(vv);
+            if constexpr (CP) {  // (the entries the stream leaves out are exact zeros)
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int g = brick_slot_pair(t);
+                    if (g >= 0) vv[t] = (rrk >> (16 + g)) & 1 ? 0.0 : vv[t];
+                }
+                // (the sums below are compiled from opaque registers, as
+                // after the wait alone, so the compiler contracts them as in
+                // the full stream's kernel; tests/test_gpu_box_zeros.py
+                // holds y to the full stream's bits)
+                sym_opaque9(vv);
+            }
             // B x_j into the row, B^T x_i into row j (lanes past the row's end
             // and the diagonal block add into their dummy slot)
             const int kk = q ? (int)((unsigned)it.kb >> 16) + lane - is : (it.kb & 0xFFFF) + lane;
@@ -557,8 +630,18 @@ __global__ __launch_bounds__(256) void k_brick_bound(int Lx, int Ly, int Lz, int
                                                      const BrickDesc *__restrict__ bd, const int *__restrict__ rowbox,
                                                      const int *__restrict__ smu, const int64_t *__restrict__ svptr,
                                                      const double *__restrict__ sval, int P,
-                                                     const int *__restrict__ owner, int *__restrict__ ebo)
+                                                     const int *__restrict__ owner, int *__restrict__ ebo,
+                                                     const int64_t *__restrict__ vptr, const int *__restrict__ rowptr,
+                                                     const int *__restrict__ rowcnt, const double *__restrict__ val)
 {
+    // (val: the compact stream holds no entry at a fixed place -- the same
+    // values from the full storage, block k0 + kk of the row; what the
+    // stream leaves out adds |0.0|)
+    auto entry = [&](int64_t i, const double *v, int t, int kk, int mu) -> double {
+        if (!val) return v[vofs(1, 9, t, kk, mu, mu)];
+        const int mp = rowptr[i + 1] - rowptr[i], m = rowcnt ? rowcnt[i] : mp;
+        return val[vptr[i] + vofs(1, 9, t, m - mu + kk, m, mp)];
+    };
     __shared__ double wred[256];
     const int b = blockIdx.x;
     const BrickDesc D = bd[b];
@@ -592,7 +675,7 @@ __global__ __launch_bounds__(256) void k_brick_bound(int Lx, int Ly, int Lz, int
                     for (int bb = 0; bb < 3; ++bb) {
                         double cs = 0.0;
 #pragma unroll
-                        for (int a = 0; a < 3; ++a) cs += fabs(v[vofs(1, 9, a * 3 + bb, kk, mu, mu)]);
+                        for (int a = 0; a < 3; ++a) cs += fabs(entry(i, v, a * 3 + bb, kk, mu));
                         bmax = fmax(bmax, cs);
                     }
                     s += bmax;
@@ -608,7 +691,7 @@ __global__ __launch_bounds__(256) void k_brick_bound(int Lx, int Ly, int Lz, int
                 double rs = 0.0;
                 for (int kk = 0; kk < mu; ++kk)
 #pragma unroll
-                    for (int bb = 0; bb < 3; ++bb) rs += fabs(v[vofs(1, 9, a * 3 + bb, kk, mu, mu)]);
+                    for (int bb = 0; bb < 3; ++bb) rs += fabs(entry(j, v, a * 3 + bb, kk, mu));
                 rmax = fmax(rmax, rs);
             }
             s += rmax;
@@ -632,9 +715,11 @@ __global__ __launch_bounds__(256) void k_brick_bound(int Lx, int Ly, int Lz, int
 // host side
 
 int brick_setup(kle_mat *A, const std::vector<int> &rb, const std::vector<int> &cnt, const std::vector<int> &srow,
-                int P, std::vector<int64_t> &svptr_out, std::string &why, void **plan_out)
+                int P, std::vector<int64_t> &svptr_out, std::string &why, void **plan_out,
+                const std::vector<unsigned char> &rbits)
 {
     auto *bp = new BrickPlan;
+    bp->rbits = rbits;
     bp->singles = g_tune.spmv_brick_singles;
     bp->pair = g_tune.spmv_brick_pair;
     const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
@@ -659,6 +744,7 @@ int brick_setup(kle_mat *A, const std::vector<int> &rb, const std::vector<int> &
             why.find("fits the LDS") == std::string::npos)
             break;
         *bp = BrickPlan{};
+        bp->rbits = rbits;
         bp->singles = g_tune.spmv_brick_singles;
         bp->pair = g_tune.spmv_brick_pair;
     }
@@ -679,6 +765,7 @@ int brick_finish(kle_mat *A, void *plan)
     std::unique_ptr<BrickPlan> bp(reinterpret_cast<BrickPlan *>(plan));
     kle_ctx *c = A->ctx;
     const int NB = (int)bp->bricks.size();
+    const bool compact = !bp->rbits.empty();
     // every address the kernel forms from the tables, checked on the host
     // first (a bad plan is an error, never a launch)
     {
@@ -715,7 +802,8 @@ int brick_finish(kle_mat *A, void *plan)
                 const int64_t rr = (int64_t)D.rstart + r;
                 if (brick_row_null(bp->rowd.data(), rr)) continue;
                 const int d = bp->rowd[2 * rr];
-                const int dbx = d & 15, dby = (d >> 4) & 15, dbz = (d >> 8) & 15;
+                const int dm = compact ? 7 : 15;
+                const int dbx = d & dm, dby = (d >> 4) & dm, dbz = (d >> 8) & dm;
                 const int bnx = (d >> 12) & 15, bny = (d >> 16) & 15, bnz = (d >> 20) & 15;
                 const int64_t i = brick_ir_node(D, brick_row_ir(bp->rowd.data(), rr), A->row_lat[0], A->row_lat[1]);
                 hmu[i] = bnx * bny * bnz - (dbx + bnx * (dby + bny * dbz));
@@ -819,7 +907,8 @@ int brick_finish(kle_mat *A, void *plan)
         hipLaunchKernelGGL(k_brick_bound, dim3((unsigned)NB), dim3(256), 0, c->stream, (int)A->row_lat[0],
                            (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
                            reinterpret_cast<const BrickDesc *>(A->d_bdesc), A->d_rowbox, dmu, A->d_svptr, A->d_sval,
-                           A->sym_P, dmu + n, A->d_stile_e);
+                           A->sym_P, dmu + n, A->d_stile_e, A->d_vptr, A->d_rowptr, A->d_rowcnt,
+                           compact ? A->d_val : nullptr);
     KLE_HIP(hipGetLastError());
     // the exponents into the descriptors
     std::vector<int> eb(NB);
@@ -846,6 +935,8 @@ int brick_finish(kle_mat *A, void *plan)
     A->brick_lds = (int)bp->lds;
     A->sws_entries = bp->ws_entries;
     A->sym_brick = 1;
+    A->brick_compact = compact;
+    A->brick_dropped = compact ? bp->dropped : 0;
     if (const char *e = getenv("KLE_TIMING"))
         if (atoi(e) && NB > 0) {
             const BrickDesc &D = bp->bricks[0];
@@ -858,6 +949,16 @@ int brick_finish(kle_mat *A, void *plan)
 }
 
 void brick_plan_free(void *plan) { delete reinterpret_cast<BrickPlan *>(plan); }
+
+void brick_pack_desc(const void *plan, const std::vector<int> &srow, std::vector<int> &pd)
+{
+    const BrickPlan *bp = reinterpret_cast<const BrickPlan *>(plan);
+    const size_t n = srow.size();
+    pd.assign(n, 0);
+    for (size_t i = 0; i < n; ++i)
+        pd[i] = brick_dw_bits(srow[i], bp->rbits.empty() ? 0 : bp->rbits[i]) | (bp->second.empty() ? 0 : bp->second[i] << 24);
+    for (int64_t i : bp->srows) pd[i] |= 1 << 25;
+}
 
 void brick_drop(kle_mat *A)
 {
@@ -876,6 +977,8 @@ void brick_forget(kle_mat *A)
     A->brick_model_us = 0.0;
     A->brick_lds = 0;
     A->sym_brick = 0;
+    A->brick_compact = 0;
+    A->brick_dropped = 0;
     A->sym_gbrick = 0;
     A->brick_lds_u = 0;
 }
@@ -908,8 +1011,14 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
         // (no brick: every row of one block, formed by the gather)
     } else {
         // (a split product's (A x, x): the bricks' shares, DOT; else the gather's)
-        if (split && dpart && !dist) go(k_nb_spmv_sym_brick<BRICK_WV, true, true>, 0, BRICK_WV);
-        else go(k_nb_spmv_sym_brick<BRICK_WV, true, false>, 0, BRICK_WV);
+        const bool dot = split && dpart && !dist;
+        if (A->brick_compact) {
+            if (dot) go(k_nb_spmv_sym_brick<BRICK_WV, true, true, true>, 0, BRICK_WV);
+            else go(k_nb_spmv_sym_brick<BRICK_WV, true, false, true>, 0, BRICK_WV);
+        } else {
+            if (dot) go(k_nb_spmv_sym_brick<BRICK_WV, true, true>, 0, BRICK_WV);
+            else go(k_nb_spmv_sym_brick<BRICK_WV, true, false>, 0, BRICK_WV);
+        }
     }
     KLE_HIP(hipGetLastError());
     // the gather (kle_sym.hip gsym_gather): per row its direct sum in y, then
@@ -947,7 +1056,8 @@ int brick_spmv_local(kle_mat *A, const kle_vec *x, kle_vec *y)
     const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
     const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
     if (A->nbricks > 0) {
-        auto kern = k_nb_spmv_sym_brick<BRICK_WV, true, false>;
+        auto kern = A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, false, true>
+                                     : k_nb_spmv_sym_brick<BRICK_WV, true, false>;
         dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * BRICK_WV), (size_t)A->brick_lds, c->stream,
                            (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp, A->brick_rstride,

@@ -26,6 +26,8 @@ static_assert(sizeof(BrickDesc) == 80, "BrickDesc layout");
 // 4 bits each) + the low byte of its region index; word 1 its value offset
 // / 16 doubles (23 bits), BRICK_ROW_NULL (a unit's absent second row) and the
 // high byte of the region index.  Rows come in units of two (kle_brick_plan.cpp).
+// (The compact value stream, below, puts a boundary bit above each of dbx,
+// dby, dbz.)
 constexpr int BRICK_ROW_NULL = 1 << 23;
 inline bool brick_row_null(const int *rowd, int64_t r) { return (rowd[2 * r + 1] & BRICK_ROW_NULL) != 0; }
 // a row descriptor's region index (the low and high bytes of its two words)
@@ -38,6 +40,46 @@ inline int64_t brick_ir_node(const BrickDesc &D, int ir, int64_t Lx, int64_t Ly)
 {
     const int rxy = D.RX * D.RY, rz = ir / rxy, rem = ir - rz * rxy, ry = rem / D.RX, rx = rem - ry * D.RX;
     return (D.ox + rx) + Lx * ((D.oy + ry) + Ly * (int64_t)(D.oz + rz));
+}
+
+// The compact value stream (spmv_brick_compact; a box K whose analytic zeros
+// are stored as exact zeros, kle_assemble.hip box_zero_entry): word 0 of a
+// row descriptor then carries, above each of dbx, dby, dbz (<= 7: 3 bits), one
+// bit "the row's coordinate on this axis is not on a domain boundary plane".
+// A block at (kx, ky, kz) of the row's box shares coordinate c with the row
+// when k_c == db_c; the off-diagonal entries (a, b) and (b, a) are left out
+// of the stream when the shared plane of a or of b counts.  Returned: bit 0
+// the pair (0,1), bit 1 (0,2), bit 2 (1,2).  The one place that decides what
+// the stream holds: the planner's sizes, the pack and the kernel's loads all
+// come here.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define KLE_BRICK_HD __host__ __device__
+#else
+#define KLE_BRICK_HD
+#endif
+KLE_BRICK_HD inline int brick_drop_bits(int dw, int kx, int ky, int kz)
+{
+    const int s0 = ((dw >> 3) & 1) & (int)(kx == (dw & 7));
+    const int s1 = ((dw >> 7) & 1) & (int)(ky == ((dw >> 4) & 7));
+    const int s2 = ((dw >> 11) & 1) & (int)(kz == ((dw >> 8) & 7));
+    return (s0 | s1) | ((s0 | s2) << 1) | ((s1 | s2) << 2);
+}
+// the pair (class) of slot t = 3 a + b: 0 (0,1), 1 (0,2), 2 (1,2); -1 the diagonal
+KLE_BRICK_HD inline int brick_slot_pair(int t) { return t == 1 || t == 3 ? 0 : t == 2 || t == 6 ? 1 : t == 5 || t == 7 ? 2 : -1; }
+// doubles a row holds in the compact stream, and how many entries it leaves out
+inline int64_t brick_row_doubles(int dw, int64_t *dropped = nullptr)
+{
+    const int dbx = dw & 7, dby = (dw >> 4) & 7, dbz = (dw >> 8) & 7;
+    const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
+    const int k0 = dbx + bnx * (dby + bny * dbz), m = bnx * bny * bnz;
+    int64_t out = 0;
+    for (int k = k0; k < m; ++k) {
+        const int kz = k / (bnx * bny), ky = (k - kz * bnx * bny) / bnx, kx = k - kz * bnx * bny - ky * bnx;
+        const int d = brick_drop_bits(dw, kx, ky, kz);
+        out += 2 * ((d & 1) + ((d >> 1) & 1) + ((d >> 2) & 1));
+    }
+    if (dropped) *dropped += out;
+    return 9 * (int64_t)(m - k0) - out;
 }
 
 constexpr int BRICK_MAX_ROUNDS = 8;        // bricks per CU the planner goes up to when fewer do not fit the LDS
@@ -58,7 +100,18 @@ struct BrickPlan {
     int singles = 0;        // (in) rows of one stored block out of the bricks, to the gather (spmv_brick_singles)
     int pair = 0;           // (in) units of two rows sharing their tails' item (spmv_brick_pair)
     std::vector<int64_t> srows;  // (out) those rows, ascending; their values (9 doubles each) after the bricks'
+    // the compact value stream: (in) per row the three "not on a boundary
+    // plane" bits (x, y, z: bits 0..2), empty: the full layout; (out) per row
+    // 1 if it is a unit's second row -- its last partial pass comes first in
+    // its stream -- and the entries the stream leaves out
+    std::vector<unsigned char> rbits, second;
+    int64_t dropped = 0;
 };
+// a row's descriptor word 0 with its boundary bits (compact stream)
+KLE_BRICK_HD inline int brick_dw_bits(int srow, int rb)
+{
+    return (srow & 0xFFFFFF) | ((rb & 1) << 3) | (((rb >> 1) & 1) << 7) | (((rb >> 2) & 1) << 11);
+}
 
 // the plan's tables checked against every address the brick kernel forms
 // from them (kle_brick_plan.cpp); nullptr: consistent, else what is wrong

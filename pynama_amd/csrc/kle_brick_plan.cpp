@@ -467,6 +467,10 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
     // instead (28,675 of 342,225 rows at config 2: 4.3 % of the items, 0.09 %
     // of the blocks).  Their values follow the bricks', 9 doubles each.
     bp.srows.clear();
+    const bool compact = !bp.rbits.empty();
+    if (compact && (int64_t)bp.rbits.size() != n) return "compact stream: one set of boundary bits per row";
+    bp.second.assign(compact ? n : 0, 0);
+    bp.dropped = 0;
     if (bp.singles) {
         std::vector<std::vector<int64_t>> kept;
         for (std::vector<int64_t> &R : best) {
@@ -559,9 +563,15 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
                 const int64_t o = voff - D.vbase;
                 if ((o >> 4) >= (1 << 23)) return "brick values beyond 2^27 doubles";
                 const int ir = (x - D.ox) + D.RX * ((y - D.oy) + D.RY * (z - D.oz));
-                bp.rowd[2 * rows] = (srow[i] & 0xFFFFFF) | ((ir & 255) << 24);
+                const int dw = compact ? brick_dw_bits(srow[i], bp.rbits[i]) : (srow[i] & 0xFFFFFF);
+                bp.rowd[2 * rows] = dw | ((ir & 255) << 24);
                 bp.rowd[2 * rows + 1] = (int)((o >> 4) | ((int64_t)((ir >> 8) & 255) << 24));
-                voff += ((int64_t)mu[i] * 9 + 15) & ~int64_t(15);
+                if (compact) {
+                    bp.second[i] = i == u.second;
+                    voff += (brick_row_doubles(dw, &bp.dropped) + 15) & ~int64_t(15);
+                } else {
+                    voff += ((int64_t)mu[i] * 9 + 15) & ~int64_t(15);
+                }
                 ++rows;
                 ++nreal;
             }
@@ -590,7 +600,7 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
 // units of two rows (the second may be null), every real row's box, first
 // block k0 < its box's size (mu >= 1 stored blocks), region index inside the
 // brick's region and its lattice node inside the owned lattice, its values
-// [off 16, off 16 + 9 mu) inside the value array, a unit's second row's
+// [off 16, off 16 + 9 mu) (the compact stream: + brick_row_doubles) inside the value array, a unit's second row's
 // values after its first's; regions within the LDS.  nullptr: consistent.
 const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t Lz, int64_t nvals,
                                   int64_t lds_cap)
@@ -609,7 +619,9 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
                 if (r % 2 == 0) return "a unit's first row is null";
                 continue;
             }
-            const int dbx = dw & 15, dby = (dw >> 4) & 15, dbz = (dw >> 8) & 15;
+            const bool compact = !bp.rbits.empty();
+            const int dm = compact ? 7 : 15;  // (compact: the nibbles' top bits are the boundary bits)
+            const int dbx = dw & dm, dby = (dw >> 4) & dm, dbz = (dw >> 8) & dm;
             const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
             const int k0 = dbx + bnx * (dby + bny * dbz), mu = bnx * bny * bnz - k0;
             if (dbx >= bnx || dby >= bny || dbz >= bnz || mu < 1) return "a row's box";
@@ -618,7 +630,8 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
             const int irz = ir / (D.RX * D.RY), irem = ir - irz * D.RX * D.RY, iry = irem / D.RX, irx = irem - iry * D.RX;
             const int64_t gx = D.ox + irx, gy = D.oy + iry, gz = D.oz + irz;
             if (gx < 0 || gx >= Lx || gy < 0 || gy >= Ly || gz < 0 || gz >= Lz) return "a row's lattice node";
-            const int64_t v0 = D.vbase + (int64_t)(vw & (BRICK_ROW_NULL - 1)) * 16, v1 = v0 + 9 * (int64_t)mu;
+            const int64_t v0 = D.vbase + (int64_t)(vw & (BRICK_ROW_NULL - 1)) * 16;
+            const int64_t v1 = v0 + (compact ? brick_row_doubles(dw & 0xFFFFFF) : 9 * (int64_t)mu);
             if (v0 < 0 || v1 > nvals) return "a row's values";
             if (r % 2 == 0) a_v0 = v0;
             else if (v0 < a_v0 || v0 - a_v0 > ((int64_t)1 << 26)) return "a unit's second row's values";

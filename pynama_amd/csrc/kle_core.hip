@@ -880,6 +880,12 @@ int kle_set_tuning(const char *key, int value)
             g_probe_ts_cap = value;
         }
 #endif
+    } else if (k == "spmv_brick_compact") {
+        KLE_ARG(value == 0 || value == 1, "spmv_brick_compact: 0 or 1");
+        g_tune.spmv_brick_compact = value;
+    } else if (k == "asm_box_zeros") {
+        KLE_ARG(value == 0 || value == 1, "asm_box_zeros: 0 or 1");
+        g_tune.asm_box_zeros = value;
     } else if (k == "spmv_sym_min_rows") {
         KLE_ARG(value >= 0, "spmv_sym_min_rows: >= 0");
         g_tune.spmv_sym_min_rows = value;
@@ -932,6 +938,8 @@ int kle_get_tuning(const char *key, int *value)
     else if (k == "spmv_brick_singles") *value = g_tune.spmv_brick_singles;
     else if (k == "spmv_brick_pair") *value = g_tune.spmv_brick_pair;
     else if (k == "elem_ghost_rows") *value = g_tune.elem_ghost_rows;
+    else if (k == "asm_box_zeros") *value = g_tune.asm_box_zeros;
+    else if (k == "spmv_brick_compact") *value = g_tune.spmv_brick_compact;
     else if (k == "spmv_gather_wps") *value = g_tune.spmv_gather_wps;
     else if (k == "spmv_gsym_brick") *value = g_tune.spmv_gsym_brick;
     else if (k == "upd_unroll") *value = g_tune.upd_unroll;

@@ -284,6 +284,8 @@ struct kle_mat {
     int nbricks = 0, brick_lds = 0, brick_gparts = 0, brick_rstride = 0;  // (gather workgroups per brick)
     int brick_dims[3] = {0, 0, 0};  // bricks along x, y, z
     double brick_model_us = 0.0;    // the planner's modelled product time
+    int brick_compact = 0;          // the bricks' value stream leaves out the analytic zeros (kle_brick.hpp)
+    int64_t brick_dropped = 0;      // ... this many entries
     void *d_bdesc = nullptr;
     int *d_browd = nullptr;
     int64_t *d_sbp = nullptr;     // per row: its first stored block in d_slid
@@ -365,7 +367,11 @@ int sym_dot_parts(const kle_mat *A);  // partials sym_spmv writes with dpart (0:
 // out; plan null + why when no brick decomposition applies), finish after the
 // values are copied (takes the plan), product, teardown
 int brick_setup(kle_mat *A, const std::vector<int> &rb, const std::vector<int> &cnt, const std::vector<int> &srow,
-                int P, std::vector<int64_t> &svptr_out, std::string &why, void **plan_out);
+                int P, std::vector<int64_t> &svptr_out, std::string &why, void **plan_out,
+                const std::vector<unsigned char> &rbits = {});  // (rbits: per row, the compact stream's boundary bits)
+// the compact stream's pack table: per row its descriptor word 0 (boundary
+// bits included) | 1 << 24 a unit's second row | 1 << 25 a one-block row of the gather
+void brick_pack_desc(const void *plan, const std::vector<int> &srow, std::vector<int> &pd);
 // the symmetric storage's value array (kle_sym.hip)
 int sval_alloc(kle_mat *A, size_t bytes);
 // a streamed array (matrix values): 0, or -1 out of memory
@@ -495,10 +501,12 @@ struct Tuning {
     int upd_unroll = 1;        // single-reduction CG update: elements per pass with their loads in flight (1, 2; 2 no faster at config 2, profiles/r05/cg_ab_upd_unroll.jsonl)
     int spmv_gsym_brick = 1;   // unstructured symmetric SpMV (read at build): row bricks (kle_gbrick.hip), 0 the 64-row groups
     int spmv_gather_wps = 0;   // run-mask gather: waves per 64-row slice (1, 2, 4; 0 auto by the runs per slice)
+    int spmv_brick_compact = 1;  // brick SpMV (read at build): a K whose analytic zeros (kle_assemble.hip box_zero_entry) are all stored as exact zeros streams the other entries alone; 0 the full 9-entry blocks
     int spmv_brick_pair = 1;  // brick SpMV (read at build): rows in units of two whose tails share one 64-lane item
     int spmv_brick_singles = 1;  // brick SpMV (read at build): rows of one stored block formed by the gather, not as 64-lane items of the bricks
     int spmv_brick_split = 0;  // brick SpMV (read at build): force nbx + 100 nby + 10000 nbz bricks (0: planned)
     int elem_ghost_rows = 1;  // element-wise K / Krhs / Rw on N > 1: a ghost-layer element's GEMM covers the 128-row groups holding its top-plane rows alone (1); 0 every group (same bits: the other rows are never gathered)
+    int asm_box_zeros = 1;  // assembly of a 3-D box mesh's free-slip K (read at assembly): the analytically zero block entries (kle_assemble.hip box_zero_entry) stored as +0.0; 0 their rounding noise (A/B and diagnosis)
     int spmv_sym_brick = 1;   // box symmetric storage, one rank (read at build): one brick per CU, sums in LDS for the whole stream (kle_brick.hip); 0 the 128-row tiles
 #ifdef KLE_PROBE_BUILD
     // timing probes (wrong results on purpose), compiled only into the probe

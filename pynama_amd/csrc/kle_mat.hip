@@ -1584,6 +1584,15 @@ int kle_mat_get_sym_bricks(const kle_mat *A, int *nbricks, int *dims, double *en
     return 0;
 }
 
+int kle_mat_get_brick_compact(const kle_mat *A, int *compact, long long *dropped_entries)
+{
+    KLE_ARG(A && compact && dropped_entries, "null arg");
+    const bool on = A->d_sval && A->sym_brick && A->brick_compact;
+    *compact = on;
+    *dropped_entries = on ? (long long)A->brick_dropped : 0;
+    return 0;
+}
+
 int kle_mat_set_symmetric(kle_mat *A, int on)
 {
     KLE_ARG(A, "null matrix");

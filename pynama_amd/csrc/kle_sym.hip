@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void k_sym_build(int64_t nrows, int Lx, int Ly
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             b[t] = v[vofs(1, 9, t, k, m, mp)];
-            sv[vofs(1, 9, t, kk, mu, mu)] = b[t];
+            if (sval) sv[vofs(1, 9, t, kk, mu, mu)] = b[t];  // (null: the compact brick stream, k_brick_pack)
             vmax = fmax(vmax, fabs(b[t]));
         }
         if (kk == 0) continue;
@@ -127,6 +127,120 @@ __global__ __launch_bounds__(256) void k_sym_build(int64_t nrows, int Lx, int Ly
         rowdiff[i] = dmax;
         rowmax[i] = vmax;
     }
+}
+
+// The compact brick stream (kle_brick.hpp brick_drop_bits): a row's position
+// in its box and its three "not on a domain boundary plane" bits (zlo / zhi:
+// this rank's lowest / highest owned plane is one: a slab's end planes
+// inside the domain are not)
+__device__ __forceinline__ int brick_row_dw(int x, int y, int z, int Lx, int Ly, int Lz, int zlo, int zhi, int bx, int by,
+                                            int bz, int bnx, int bny, int bnz, int &rbits)
+{
+    rbits = (int)(x > 0 && x < Lx - 1) | (int)(y > 0 && y < Ly - 1) << 1 |
+            (int)(!(zlo && z == 0) && !(zhi && z == Lz - 1)) << 2;
+    return brick_dw_bits((x - bx) | (y - by) << 4 | (z - bz) << 8 | bnx << 12 | bny << 16 | bnz << 20, rbits);
+}
+
+// The check that decides the compact stream: over every owned row's stored
+// (upper) blocks, cnt[0] the entries the stream would leave out that are not
+// +0.0 (any bit set); the rows' bits to rbits.
+__global__ __launch_bounds__(256) void k_brick_zero_check(int64_t nrows, int Lx, int Ly, int Lz, int zo, int zlo, int zhi,
+                                                          const int *__restrict__ rowptr,
+                                                          const int *__restrict__ rowcnt,
+                                                          const int *__restrict__ rowbox,
+                                                          const int64_t *__restrict__ vptr,
+                                                          const double *__restrict__ val,
+                                                          unsigned long long *__restrict__ cnt,
+                                                          unsigned char *__restrict__ rbits)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nrows) return;
+    const int64_t Lxy = (int64_t)Lx * Ly;
+    const int z = (int)(i / Lxy), y = (int)((i - z * Lxy) / Lx), x = (int)(i - z * Lxy - (int64_t)y * Lx);
+    int bx, by, bz, bnx, bny, bnz, rb;
+    sym_box(rowbox, i, Lx, Lxy, bx, by, bz, bnx, bny, bnz);
+    bz -= zo;
+    const int dw = brick_row_dw(x, y, z, Lx, Ly, Lz, zlo, zhi, bx, by, bz, bnx, bny, bnz, rb);
+    if (lane == 0) rbits[i] = (unsigned char)rb;
+    const int m = rowcnt ? rowcnt[i] : rowptr[i + 1] - rowptr[i], mp = rowptr[i + 1] - rowptr[i];
+    const int k0 = (x - bx) + bnx * ((y - by) + bny * (z - bz));
+    const double *v = val + vptr[i];
+    unsigned bad = 0;
+    for (int k = k0 + lane; k < m; k += 64) {
+        const int bnxy = bnx * bny;
+        const int kz = k / bnxy, ky = (k - kz * bnxy) / bnx, kx = k - kz * bnxy - ky * bnx;
+        const int db = brick_drop_bits(dw, kx, ky, kz);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int g = brick_slot_pair(t);
+            if (g < 0 || !((db >> g) & 1)) continue;
+            bad += __double_as_longlong(v[vofs(1, 9, t, k, m, mp)]) != 0ll;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    if (lane == 0 && bad) atomicAdd(cnt, (unsigned long long)bad);
+}
+
+// The compact brick stream of every row (pd: kle_brick.hip brick_pack_desc),
+// in the order k_nb_spmv_sym_brick<.., CP> walks it: the row's passes of 64
+// blocks, each slot-major with the kept lanes' values in lane order; the
+// last partial pass last, or first in a unit's second row.  A one-block row
+// of the gather keeps its 9 doubles.
+__global__ __launch_bounds__(256) void k_brick_pack(int64_t nrows, int Lx, int Ly, int zo, const int *__restrict__ rowptr,
+                                                    const int *__restrict__ rowcnt, const int *__restrict__ rowbox,
+                                                    const int64_t *__restrict__ vptr, const double *__restrict__ val,
+                                                    const int *__restrict__ pd, const int64_t *__restrict__ svptr,
+                                                    double *__restrict__ sval)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nrows) return;
+    const int64_t Lxy = (int64_t)Lx * Ly;
+    const int z = (int)(i / Lxy), y = (int)((i - z * Lxy) / Lx), x = (int)(i - z * Lxy - (int64_t)y * Lx);
+    int bx, by, bz, bnx, bny, bnz;
+    sym_box(rowbox, i, Lx, Lxy, bx, by, bz, bnx, bny, bnz);
+    bz -= zo;
+    const int m = rowcnt ? rowcnt[i] : rowptr[i + 1] - rowptr[i], mp = rowptr[i + 1] - rowptr[i];
+    const int k0 = (x - bx) + bnx * ((y - by) + bny * (z - bz));
+    const int mu = m - k0;
+    const double *v = val + vptr[i];
+    double *sv = sval + svptr[i];
+    const int d = pd[i], dw = d & 0xFFFFFF;
+    if ((d >> 25) & 1) {
+        if (lane < 9) sv[lane] = v[vofs(1, 9, lane, k0, m, mp)];
+        return;
+    }
+    const int full = mu & ~63, tail = mu - full;
+    const bool second = (d >> 24) & 1;
+    int off = 0;
+    auto part = [&](int kb, int nb) {
+        const bool act = lane < nb;
+        const int k = k0 + min(kb + lane, mu - 1);
+        const int bnxy = bnx * bny;
+        const int kz = k / bnxy, ky = (k - kz * bnxy) / bnx, kx = k - kz * bnxy - ky * bnx;
+        const int db = brick_drop_bits(dw, kx, ky, kz);
+        const bool kp[4] = {act, act && !(db & 1), act && !(db & 2), act && !(db & 4)};
+        int n[4], c[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const unsigned long long bl = __ballot(kp[g]);
+            n[g] = __popcll(bl);
+            c[g] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bl, 0u));
+        }
+        int sb = 0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int g = brick_slot_pair(t) + 1;
+            if (kp[g]) sv[off + sb + c[g]] = v[vofs(1, 9, t, k, m, mp)];
+            sb += n[g];
+        }
+        off += sb;
+    };
+    if (second && tail) part(full, tail);
+    for (int kb = 0; kb < full; kb += 64) part(kb, 64);
+    if (!second && tail) part(full, tail);
 }
 
 // Same tile pass with the wave's (row, 64-block pass) items flattened into one
@@ -1903,6 +2017,14 @@ static int sym_probe(kle_mat *A, double vmax_all, bool &bad)
 // rank decides the same way (any_rank), so no rank runs the symmetric SpMV
 // and its reverse halo while a neighbour runs the full storage.
 static int sym_build_impl(kle_mat *A);
+// a device scratch buffer freed when its scope ends
+struct DevFree {
+    void *&p;
+    ~DevFree()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
 
 // Every error return of the builders, wherever it happens (a refused check,
 // a device error between the allocations and the last check), leaves A
@@ -1940,6 +2062,7 @@ static int sym_build_impl(kle_mat *A)
     int64_t rlo[NSH][2] = {{0, 0}, {0, 0}, {0, 0}},
             rhi[NSH][3] = {{SYM_TX - 1, 3, 3}, {SYM_TX - 1, 7, 1}, {SYM_TX - 1, 1, 3}};
     int64_t tot = 0, blocks = 0, all = 0, up_ghost = 0, lo_ghost = 0;
+    int64_t dbmax = 0;  // (the rows' largest offset in their boxes: 3 bits in the compact stream's descriptors)
     if (why.empty()) {
         rb.resize(2 * n);
         rp.resize(n + 1);
@@ -1970,6 +2093,7 @@ static int sym_build_impl(kle_mat *A)
                 break;
             }
             srow[i] = (int)((x - bx) | (y - by) << 4 | (z - bz) << 8) | bnx << 12 | bny << 16 | bnz << 20;
+            dbmax = std::max<int64_t>(dbmax, std::max({x - bx, y - by, z - bz}));
             {
                 // the upper triangle's extent: the planes above take the
                 // whole box, the row's own plane the lines from its own on
@@ -2006,6 +2130,7 @@ static int sym_build_impl(kle_mat *A)
     // one rank, no ghosts: bricks (kle_brick.hip) -- the values go in brick
     // order, and none of the tile set-up below is needed
     void *bplan = nullptr;
+    bool compact = false;  // (the bricks' compact value stream)
     struct PlanGuard {
         void *&p;
         ~PlanGuard() { brick_plan_free(p); }
@@ -2014,7 +2139,31 @@ static int sym_build_impl(kle_mat *A)
     if (why.empty() && g_tune.spmv_sym_brick && g_tune.spmv_sym_det && (c->nranks == 1 ? zo == 0 && hp == 0 : !A->plan)) {
         std::string bwhy;
         std::vector<int64_t> svb;
-        KLE_TRY(brick_setup(A, rb, cnt, srow, P, svb, bwhy, &bplan));
+        // the compact value stream: only where every entry it would leave out
+        // is stored as +0.0 (the check decides, on every rank alike)
+        std::vector<unsigned char> rbits;
+        if (g_tune.spmv_brick_compact) {
+            unsigned long long *dc = nullptr, hc = 1;
+            unsigned char *db = nullptr;
+            DevFree fdc{(void *&)dc}, fdb{(void *&)db};  // (freed on every way out)
+            const bool mem = hipMalloc(&dc, sizeof(hc)) == hipSuccess && hipMalloc(&db, std::max<int64_t>(n, 1)) == hipSuccess;
+            (void)hipGetLastError();
+            if (mem && dbmax <= 7 && n > 0) {
+                KLE_HIP(hipMemsetAsync(dc, 0, sizeof(hc), c->stream));
+                hipLaunchKernelGGL(k_brick_zero_check, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, n, (int)Lx,
+                                   (int)Ly, (int)Lz, (int)zo, (int)(A->lo_rank < 0), (int)(A->hi_rank < 0), A->d_rowptr,
+                                   A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dc, db);
+                KLE_HIP(hipGetLastError());
+                KLE_HIP(hipStreamSynchronize(c->stream));
+                KLE_HIP(hipMemcpy(&hc, dc, sizeof(hc), hipMemcpyDeviceToHost));
+                rbits.resize(n);
+                KLE_HIP(hipMemcpy(rbits.data(), db, n, hipMemcpyDeviceToHost));
+            }
+            bool no = false;
+            KLE_TRY(any_rank(c, hc != 0 || rbits.empty(), no));
+            if (no) rbits.clear();
+        }
+        KLE_TRY(brick_setup(A, rb, cnt, srow, P, svb, bwhy, &bplan, rbits));
         bool none = false;
         KLE_TRY(any_rank(c, !bplan, none));
         if (none && bplan) {
@@ -2024,7 +2173,8 @@ static int sym_build_impl(kle_mat *A)
         }
         if (bplan) {
             sv.swap(svb);
-            tot = std::max<int64_t>(tot, sv[n]);
+            tot = rbits.empty() ? std::max<int64_t>(tot, sv[n]) : sv[n];
+            compact = !rbits.empty();
         }
         else if (const char *e = getenv("KLE_TIMING"))
             if (atoi(e)) fprintf(stderr, "[kle brick r%d] not used: %s\n", c->rank, bwhy.c_str());
@@ -2086,9 +2236,27 @@ static int sym_build_impl(kle_mat *A)
         KLE_TRY(h2d(A->d_svptr, sv.data(), sizeof(int64_t) * (n + 1)));
         KLE_TRY(h2d(A->d_srow, srow.data(), sizeof(int) * n));
         hipLaunchKernelGGL(k_sym_build, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, n, (int)Lx, (int)Ly,
-                           (int)zo, A->d_rowptr, A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, A->d_svptr, A->d_sval,
-                           rowdiff, rowmax);
+                           (int)zo, A->d_rowptr, A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, A->d_svptr,
+                           compact ? nullptr : A->d_sval, rowdiff, rowmax);
         KLE_HIP(hipGetLastError());
+        if (compact) {
+            std::vector<int> pd;
+            brick_pack_desc(bplan, srow, pd);
+            int *dpd = nullptr;
+            DevFree fpd{(void *&)dpd};
+            if (hipMalloc(&dpd, sizeof(int) * std::max<int64_t>(n, 1)) != hipSuccess) {
+                (void)hipGetLastError();
+                nomem = 1;
+            } else {
+                KLE_TRY(h2d(dpd, pd.data(), sizeof(int) * n));
+                KLE_HIP(hipMemsetAsync(A->d_sval, 0, sizeof(double) * std::max<int64_t>(tot, 1), c->stream));
+                hipLaunchKernelGGL(k_brick_pack, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, n, (int)Lx,
+                                   (int)Ly, (int)zo, A->d_rowptr, A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dpd,
+                                   A->d_svptr, A->d_sval);
+                KLE_HIP(hipGetLastError());
+                KLE_HIP(hipStreamSynchronize(c->stream));
+            }
+        }
         std::vector<double> hd(n), hm(n);
         KLE_HIP(hipStreamSynchronize(c->stream));
         KLE_HIP(hipMemcpy(hd.data(), rowdiff, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -2348,7 +2516,8 @@ std::string sym_kernel_name(const kle_mat *A)
 // update's
 double brick_split_bytes(const kle_mat *A)
 {
-    return (double)A->sblocks * 72.0 + A->nrows * (8.0 + 48.0) + (double)A->sws_entries * 24.0;
+    return (double)A->sblocks * 72.0 - 8.0 * (double)A->brick_dropped + A->nrows * (8.0 + 48.0) +
+           (double)A->sws_entries * 24.0;
 }
 
 double sym_spmv_bytes(const kle_mat *A)
@@ -2359,7 +2528,10 @@ double sym_spmv_bytes(const kle_mat *A)
     // entries, are not counted)
     // bricks: values, 8 B of row descriptor per row, x and y once, each
     // brick's region sums written once and read once
-    if (A->sym_brick) return (double)A->sblocks * 72.0 + A->nrows * (8.0 + 48.0) + (double)A->sws_entries * 48.0;
+    // (a compact stream: less the entries it leaves out)
+    if (A->sym_brick)
+        return (double)A->sblocks * 72.0 - 8.0 * (double)A->brick_dropped + A->nrows * (8.0 + 48.0) +
+               (double)A->sws_entries * 48.0;
     // graph bricks: values + positions, 16 B of row descriptor per row, x
     // and y once, per dictionary entry its node id and its sums written and
     // read once

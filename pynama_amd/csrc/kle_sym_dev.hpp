@@ -109,6 +109,15 @@ __device__ __forceinline__ void sym_wait9(double *v)
                  : "i"(N));
 }
 
+// Nine registers made opaque to the compiler (no instruction): what is
+// computed from them afterwards is compiled as from asm results
+__device__ __forceinline__ void sym_opaque9(double *v)
+{
+    asm volatile(""
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                   "+v"(v[8]));
+}
+
 // One load of x for a brick's region fill (SGPR base + 32-bit byte offset),
 // in inline asm like the value loads: issued before the first items' value loads, it is waited for with
 // an explicit vmcnt that leaves those in flight (a compiler load would be

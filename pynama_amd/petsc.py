@@ -531,7 +531,10 @@ class Mat:
         call("kle_mat_get_sym_bricks", self._h, C.byref(n), dims, C.byref(ent), C.byref(mus))
         if n.value == 0:
             return None
-        return {"bricks": n.value, "dims": list(dims), "region_entries_per_row": ent.value, "model_us": mus.value}
+        cp, dr = C.c_int(), C.c_longlong()
+        call("kle_mat_get_brick_compact", self._h, C.byref(cp), C.byref(dr))
+        return {"bricks": n.value, "dims": list(dims), "region_entries_per_row": ent.value, "model_us": mus.value,
+                "compact": bool(cp.value), "dropped_entries": dr.value}
 
     def moveValues(self, shift, fresh=True):
         """Diagnostic: the symmetric storage's values `shift` bytes into a

@@ -27,8 +27,12 @@ def median(d, name):
     dispatch list is the bench matrix's value."""
     f = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)[0]
     want = name.replace(" ", "") + "("  # (rocprofv3 names carry "void kle::" and the argument list)
+    # (the brick kernel on the compact value stream is the same reported
+    # kernel with one more template argument, kle_brick.hip CP)
+    alt = want[:-2] + ",true>(" if want.startswith("k_nb_spmv_sym_brick<") else want
     v = [float(r["Counter_Value"]) for r in csv.DictReader(open(f))
-         if want in r["Kernel_Name"].replace(" ", "").replace("voidkle::", "").replace("kle::", "")]
+         if any(w in r["Kernel_Name"].replace(" ", "").replace("voidkle::", "").replace("kle::", "")
+                for w in (want, alt))]
     if not v:
         raise SystemExit(f"pmc_traffic: no dispatch of {name} in {f}")
     v.sort()
