@@ -436,6 +436,50 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * unstructured meshes, no-slip meshes and a mesh whose nranks is not the
  * context's. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* Sum-factorised element-wise K (which 0) or Krhs (which 1) of any one-rank
+ * mesh, kind 0 (box) or kind 1 (unstructured), 2-D or 3-D, ngl 2..8, with its
+ * Dirichlet set: no stored values and no element matrix.  The factored form of
+ * the element matrix,
+ *     K_e(la, mb) = d_ab G_lm + a_d D_ab(l,m) + a_w (d_ab tr D(l,m) - D_ba(l,m)),
+ *     G_lm = sum_full c_q grad N_l . grad N_m,  D_ab(l,m) = sum_red c_q d_a N_l d_b N_m,
+ * applied to a vector is a quadrature-point evaluation with per-point
+ * geometry: with (grad u)_ab = d_b u^a at the point,
+ *     (K_e u)_l^a =  sum_{q in full} c_q sum_b d_b N_l(q) (grad u)_ab(q)
+ *                  + sum_{q in red}  c_q sum_b d_b N_l(q) T_ab(q),
+ *     T = a_d (div u) I + a_w (grad u - grad u^T),
+ * and both sums factorise into 1-D passes with the h / dh tables of the rules
+ * (full: GLL(ngl) for ngl > 3, else Gauss(ngl); reduced: Gauss(ngl - 1)).
+ * k_sumfac_elem gathers a batch of whole elements' x through the connectivity
+ * into LDS (mask folded in as -1: K drops the Dirichlet columns, Krhs keeps
+ * only them; a dropped entry of x is never read, so an Inf or NaN there
+ * reaches no result), runs the passes, the point stage (inv J, flux, inv J^T)
+ * and the transposed passes for the full and then the reduced rule and stores
+ * the element results (negated for Krhs); k_sumfac_gather sums a node's
+ * incidence entries -- a CSR list, a node may lie in any number of elements --
+ * in ascending element order; Dirichlet rows give y_i = x_i.  No atomics: the
+ * same input gives the same bits.  c_q and inv J are read from two tables
+ * [e][q][1 + dim^2] filled at creation by the assembly's geometry kernel from
+ * the mesh's own corners.
+ * Memory: the two geometry tables (8 E (ngl^dim + (ngl-1)^dim) (1 + dim^2)
+ * bytes), E dim ngl^dim doubles of element results, the connectivity and the
+ * incidence list (4 bytes per element node each), the diagonal (dim N
+ * doubles, formed once at creation; 1 on Dirichlet rows, 0 on the free rows of
+ * Krhs) and one flag per node.
+ * The result is a kle_mat of format 2 ("elem") with the call surface of
+ * kle_mat_create_kle_element's K and Krhs: kle_mat_mult, kle_mat_mult_add,
+ * kle_mat_get_diagonal, the size and ownership getters, kle_mat_get_info
+ * (nz_used 0), kle_mat_spmv_bytes, kle_mat_spmv_kernel
+ * ("k_sumfac_elem<D>+k_sumfac_gather<D>"), kle_mat_time_local_spmv and
+ * kle_ksp_set_operators with cg (classic and single reduction: the generic
+ * paths), pipecg or gmres and PC none or jacobi.  Calls that need stored
+ * values, and kle_mat_copy_dirichlet_rows, return KLE_ERR_SUP.
+ * KLE_ERR_SUP also for which 2 (Rw), no-slip meshes, a mesh whose nranks is
+ * not the context's and any mesh with nranks > 1; KLE_ERR_ARG for any other
+ * which.  Every table index is checked on the host before upload
+ * (connectivity inside the mesh, incidence consistent with it and ascending,
+ * E ngl^dim and dim N below 2^31): a bad table is an error code, never a
+ * launch. */
+int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Element-wise no-slip operator of a uniform box mesh: the matrices of
  * kle_assemble_ns (MatNS.buildNS, mat_ns.py:47-145) with no stored values.
  * which: 0 K, 1 Krhs, 2 Rw, 3 Kfs, 4 Krhsfs, 5 Rwfs, 6 K + Kfs (the operator

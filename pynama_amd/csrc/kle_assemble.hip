@@ -1361,6 +1361,24 @@ static int element_matrices(kle_ctx *ctx, const kle_mesh *m, double **dKe, doubl
     return 0;
 }
 
+// The Gauss-point geometry of every local element at the full and the reduced
+// rule, [e][q][1 + dim^2] each (c_q = w_q det J, inv J): the tables the element
+// kernels above read, from the mesh's own corners, handed to the caller (who
+// frees both) for the sum-factorised operator (kle_sumfac.hip).
+int element_geometry(kle_ctx *ctx, const kle_mesh *m, double **gF, double **gR, int *npF, int *npR)
+{
+    *gF = *gR = nullptr;
+    ElemSetup S;
+    KLE_TRY(element_setup(ctx, m, S));
+    KLE_HIP(hipStreamSynchronize(ctx->stream));
+    *gF = S.gF;
+    *gR = S.gR;
+    S.gF = S.gR = nullptr;
+    *npF = S.T.F.np1;
+    *npR = S.T.R.np1;
+    return 0;
+}
+
 // K_e of the first local element alone, as blocks [l][m][a][b] in a new device
 // buffer: the geometry and element kernels of the assembly on that element's
 // own corners, so the values are the ones the assembled K received from it

@@ -205,6 +205,7 @@ struct kle_vec {
 namespace kle {
 struct ElemOp;    // kle_elem.hip: the element-wise operator of a uniform box mesh
 struct CollocOp;  // kle_colloc.hip: an element-wise collocation operator (Curl, SrT, DivSrT)
+struct SumfacOp;  // kle_sumfac.hip: the sum-factorised K / Krhs of any one-rank mesh
 }
 
 struct kle_mat {
@@ -212,6 +213,7 @@ struct kle_mat {
     int kind = 0;  // 0 node-block, 1 scalar AIJ, 2 element-wise (no stored values: elem)
     kle::ElemOp *elem = nullptr;  // kind 2
     kle::CollocOp *colloc = nullptr;  // kind 2, instead of elem: Curl / SrT / DivSrT (kle_colloc.hip)
+    kle::SumfacOp *sumfac = nullptr;  // kind 2, instead of elem: sum-factorised K / Krhs (kle_sumfac.hip)
     // kind 2: el_n local elements -- [0, el_ghost) the ghost layer below, [el_ghost, el_int1) those reading
     // owned nodes alone (run beside the halo), [el_int1, el_n) the top layer reading the upper ghost plane
     int64_t el_n = 0, el_ghost = 0, el_int1 = 0;
@@ -456,6 +458,15 @@ int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, boo
 void colloc_drop(kle_mat *A);
 double colloc_spmv_bytes(const kle_mat *A);
 std::string colloc_kernel_name(const kle_mat *A);
+// sum-factorised K and Krhs (kle_sumfac.hip; kle_mat kind 2 with sumfac set)
+int element_geometry(kle_ctx *ctx, const kle_mesh *m, double **gF, double **gR, int *npF, int *npR);  // kle_assemble.hip
+int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+int sumfac_diagonal(const kle_mat *A, kle_vec *d);
+void sumfac_drop(kle_mat *A);
+double sumfac_spmv_bytes(const kle_mat *A);
+std::string sumfac_kernel_name(const kle_mat *A);
+int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &incp, const std::vector<int32_t> &inc,
+                    int64_t E, int64_t N, int nn, int dim);
 // kind 2 holds no assembled values: the calls that need them end here
 #define KLE_NO_ELEM(A, what)                                                                              \
     do {                                                                                                  \

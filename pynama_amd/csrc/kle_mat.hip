@@ -764,7 +764,7 @@ int spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
     std::pair<hipEvent_t, hipEvent_t> ev;
     if (A->kind == 2) {
         KLE_TRY(c->tic("spmv", &ev));
-        KLE_TRY(A->colloc ? colloc_spmv(A, x, y, istate) : elem_spmv(A, x, y, istate));
+        KLE_TRY(A->sumfac ? sumfac_spmv(A, x, y, istate) : A->colloc ? colloc_spmv(A, x, y, istate) : elem_spmv(A, x, y, istate));
         KLE_TRY(c->toc("spmv", &ev));
         return 0;
     }
@@ -1087,6 +1087,7 @@ int kle_mat_destroy(kle_mat *A)
     if (!A) return 0;
     elem_drop(A);
     colloc_drop(A);
+    sumfac_drop(A);
     hipFree(A->d_rowcnt);
     hipFree(A->d_rowbox);
     hipFree(A->d_vptr);
@@ -1232,7 +1233,7 @@ int kle_mat_get_diagonal(const kle_mat *A, kle_vec *d)
     KLE_ARG(d->n_local == A->m_local, "diagonal vector size mismatch");
     if (A->kind == 2 && A->colloc)
         return fail(KLE_ERR_SUP, "getDiagonal: an element-wise collocation operator holds no diagonal");
-    if (A->kind == 2) return elem_diagonal(A, d);
+    if (A->kind == 2) return A->sumfac ? sumfac_diagonal(A, d) : elem_diagonal(A, d);
     kle_ctx *c = A->ctx;
     if (A->kind == 0) {
         KLE_ARG(A->R == A->C, "get_diagonal needs square blocks");
@@ -1645,7 +1646,7 @@ int kle_mat_spmv_kernel(const kle_mat *A, char *buf, int buflen)
     KLE_ARG(A && buf && buflen > 0, "bad arg");
     std::string s;
     if (A->kind == 2) {
-        s = A->colloc ? colloc_kernel_name(A) : elem_kernel_name(A);
+        s = A->sumfac ? sumfac_kernel_name(A) : A->colloc ? colloc_kernel_name(A) : elem_kernel_name(A);
     } else if (A->kind != 0) {
         s = "k_aij_spmv<8,4>";
     } else if (A->d_sval && g_tune.spmv_sym) {
@@ -1669,7 +1670,7 @@ int kle_mat_spmv_bytes(const kle_mat *A, double *bytes)
 {
     KLE_ARG(A && bytes, "null arg");
     if (A->kind == 2) {
-        *bytes = A->colloc ? colloc_spmv_bytes(A) : elem_spmv_bytes(A);
+        *bytes = A->sumfac ? sumfac_spmv_bytes(A) : A->colloc ? colloc_spmv_bytes(A) : elem_spmv_bytes(A);
     } else if (A->kind == 0 && A->d_sval && g_tune.spmv_sym) {
         *bytes = sym_spmv_bytes(A);
     } else if (A->kind == 0) {
@@ -1700,6 +1701,7 @@ int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, 
     // an element-wise operator: this rank's element launches and its gather
     auto local = [&]() {
         return A->kind != 2 ? brick_spmv_local(A, x, y)
+               : A->sumfac  ? sumfac_spmv(A, x, y, nullptr)  // (one rank: no halo to leave out)
                : A->colloc  ? colloc_spmv(A, x, y, nullptr, true)
                             : elem_spmv(A, x, y, nullptr, true);
     };

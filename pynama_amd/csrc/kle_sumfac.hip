@@ -1,0 +1,668 @@
+// kle_sumfac.hip -- sum-factorised element-wise K and Krhs on any one-rank
+// mesh, box or unstructured (kle_mat kind 2 with sumfac set): no assembled
+// values and no element matrix.
+//
+// On distorted hexes the element matrices differ, so the one K_e0 of
+// kle_elem.hip is gone; the factored form of the assembly (kle_assemble.hip
+// store_elem_blocks) applied to a vector is a quadrature-point evaluation with
+// per-point geometry.  With (grad u)_ab = d_b u^a at the point:
+//
+//     (K_e u)_l^a =  sum_{q in full} c_q sum_b d_b N_l(q) (grad u)_ab(q)
+//                  + sum_{q in red}  c_q sum_b d_b N_l(q) T_ab(q)
+//     T = a_d (div u) I + a_w (grad u - grad u^T)
+//
+// and the tensor structure of N turns both sums into 1-D passes with the h / dh
+// tables of kle_basis (full: GLL(ngl) for ngl > 3, else Gauss(ngl); reduced:
+// Gauss(ngl - 1)).
+//
+//   k_sumfac_elem<DIM>    a 256-thread workgroup takes a batch of whole
+//       elements (as many as fit 256 threads, at least one) and gathers their
+//       x entries through the connectivity into LDS, component-major tiles
+//       [element][k][j][i] with the odd line, plane and element strides of
+//       kle_colloc.hip.  The mask is folded into the connectivity as -1 (K: the
+//       Dirichlet columns, Krhs: the free ones): such an entry is 0 and x is
+//       never read there.  The four 1-D tables sit in LDS (row stride 9).  One
+//       thread per (element, lattice site), looping where an element has more
+//       than 256 sites (ngl 7, 8 in 3-D); a site is a node or, along the
+//       directions already contracted, a point (sites beyond the rule's points
+//       idle).  Per rule, full first:
+//         forward, per component: x pass (h u, dh u), y pass, z pass -> the
+//           reference gradient of the component at the thread's point, m
+//           ascending in every line sum;
+//         point: grad u = sum_k invJ[b][k] g_ref[a][k] (as fill_chunk), the
+//           flux c grad u (full) or c T (reduced), back with invJ^T;
+//         transposed, per component: z, y, x passes with the tables read
+//           transposed, q ascending; the x pass leaves the node's sum.
+//       The reduced rule's sum is added to the full rule's; ws[e][l][a] takes
+//       it, negated for Krhs.
+//   k_sumfac_gather<DIM>  one thread per owned DoF: the sum of its node's
+//       incidence entries of ws, a CSR list (inc_ptr, inc_idx = e nn + l,
+//       ascending e -- a Gmsh node lies in any number of elements).  Dirichlet
+//       rows: y_i = x_i.
+//   k_sumfac_diag<DIM>    once at creation: the element diagonal
+//         sum_full c |grad N_l|^2 + sum_red c [a_d (d_a N_l)^2 + a_w (|grad N_l|^2 - (d_a N_l)^2)]
+//       per (element, node), gathered like the product; 1 on Dirichlet rows, 0
+//       on the free rows of Krhs.
+//
+// c_q and inv J come from two tables [e][q][1 + dim^2], one per rule, that the
+// assembly's k_geometry fills from the mesh's own corners: the numbers the
+// assembled matrix was formed from.  No atomics, fixed order: the same input
+// gives the same bits.  Both product kernels do nothing once the Krylov reason
+// word is set.  One rank only: the index-list halos of a graph partition are
+// not handled.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "kle_basis.hpp"
+#include "kle_internal.hpp"
+
+namespace kle {
+
+constexpr int SF_SD = 9;      // row stride of a 1-D table in LDS (odd, >= 8)
+constexpr int SF_ST = 8 * SF_SD;  // doubles per table in LDS
+constexpr int SF_SC3 = 584;   // doubles per tile, 3-D: one ngl 8 element, strides 9 / 73 / 584
+constexpr int SF_SC2 = 448;   // 2-D: 64 ngl 2 elements, strides 3 / 7
+constexpr double SF_ALPHA_W = 1e2, SF_ALPHA_D = 1e3;  // kle_assemble.hip ALPHA_W, ALPHA_D (spectral.py:96-97)
+
+struct SumfacOp {
+    int which = 0, dim = 3, ngl = 0, nn = 0, negate = 0;
+    int neb = 1, sy = 0, sz = 0, se = 0;  // elements per workgroup; LDS line, plane and element strides
+    int npF = 0, npR = 0;       // 1-D points of the full and the reduced rule
+    int64_t E = 0, N = 0, ninc = 0;
+    double *d_tab = nullptr;    // [4][8][8] h, dh of the full rule, h, dh of the reduced rule: [q][a], row length ngl
+    double *d_geoF = nullptr;   // [E][npF^dim][1 + dim^2] c_q, inv J
+    double *d_geoR = nullptr;   // [E][npR^dim][1 + dim^2]
+    double *d_ws = nullptr;     // [E][nn][dim] element results
+    double *d_diag = nullptr;   // [N dim] the diagonal, formed at creation
+    int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order; -1 where the operator drops the entry
+    int32_t *d_incp = nullptr;  // [N + 1] node -> its entries of d_inc
+    int32_t *d_inc = nullptr;   // [E nn] e * nn + l, ascending e per node
+    uint8_t *d_dir = nullptr;   // [N] Dirichlet flag
+};
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
+                                                     int negate, const double *__restrict__ tab,
+                                                     const double *__restrict__ geoF, const double *__restrict__ geoR,
+                                                     const int32_t *__restrict__ conn, const double *__restrict__ x,
+                                                     double *__restrict__ ws, const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    constexpr int NIT = DIM == 3 ? 2 : 1;  // sites per thread: 512 at ngl 8 in 3-D
+    constexpr int G1 = 1 + DIM * DIM, SC = DIM == 3 ? SF_SC3 : SF_SC2;
+    __shared__ double sx[DIM * SC];                 // x, per component
+    __shared__ double sA[2 * SC];                   // after the x pass: (h u, dh u); before the transposed x pass
+    __shared__ double sB[DIM * SC];                 // after the y pass (3-D); the point fluxes
+    __shared__ double sC[DIM == 3 ? 3 * SC : 1];    // after the transposed z pass (3-D)
+    __shared__ double sd[4 * SF_ST];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * neb;
+    const int nt = (int)min((int64_t)neb, E - e0) * nn;  // (element, site) pairs of this batch
+    const int64_t t0 = e0 * nn;
+    {
+        const int n2 = ngl * ngl;
+        for (int t = tid; t < 4 * n2; t += 256) {
+            const int tb = t / n2, r = t - tb * n2;
+            sd[tb * SF_ST + (r / ngl) * SF_SD + r % ngl] = tab[tb * 64 + r];
+        }
+    }
+    bool ok[NIT];
+    int base[NIT], si[NIT], sj[NIT], sk[NIT], sel[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int t = tid + it * 256;
+        ok[it] = t < nt;
+        const int el = t / nn, l = t - el * nn;
+        const int r = l / ngl;
+        si[it] = l % ngl;
+        sj[it] = DIM == 3 ? r % ngl : r;
+        sk[it] = DIM == 3 ? r / ngl : 0;
+        sel[it] = el;
+        base[it] = el * se + sk[it] * sz + sj[it] * sy + si[it];
+        if (ok[it]) {
+            const int node = conn[t0 + t];
+#pragma unroll
+            for (int b = 0; b < DIM; ++b) {
+                double v = 0.0;
+                if (node >= 0) v = x[(int64_t)node * DIM + b];  // (a dropped entry is never read)
+                sx[b * SC + base[it]] = v;
+            }
+        }
+    }
+    double res[NIT][DIM];
+    double g[NIT][DIM][DIM];  // [component][reference direction]: the gradient, then the flux
+    for (int rule = 0; rule < 2; ++rule) {
+        const int P = rule ? ngl - 1 : ngl;
+        const double *th = sd + rule * 2 * SF_ST, *tdh = th + SF_ST;
+        const double *geo = rule ? geoR : geoF;
+        const int nq = DIM == 3 ? P * P * P : P * P;
+        __syncthreads();  // x and the tables; the last rule's reads of sA
+        // ---- forward: reference gradient of every component at the points
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int i = si[it], o = a * SC + base[it] - i;
+                double ah = 0.0, ad = 0.0;
+                for (int m = 0; m < ngl; ++m) {
+                    const double v = sx[o + m];
+                    ah += th[i * SF_SD + m] * v;
+                    ad += tdh[i * SF_SD + m] * v;
+                }
+                sA[base[it]] = ah;
+                sA[SC + base[it]] = ad;
+            }
+            __syncthreads();
+            if constexpr (DIM == 2) {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int j = sj[it], o = base[it] - j * sy;
+                    double g0 = 0.0, g1 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        g0 += th[j * SF_SD + m] * sA[SC + o + m * sy];
+                        g1 += tdh[j * SF_SD + m] * sA[o + m * sy];
+                    }
+                    g[it][a][0] = g0;
+                    g[it][a][1] = g1;
+                }
+                __syncthreads();  // the next component's x pass rewrites sA
+            } else {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int j = sj[it], o = base[it] - j * sy;
+                    double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        const double ah = sA[o + m * sy], ad = sA[SC + o + m * sy];
+                        const double hj = th[j * SF_SD + m], dj = tdh[j * SF_SD + m];
+                        b0 += hj * ad;
+                        b1 += dj * ah;
+                        b2 += hj * ah;
+                    }
+                    sB[base[it]] = b0;
+                    sB[SC + base[it]] = b1;
+                    sB[2 * SC + base[it]] = b2;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+                    const int k = sk[it], o = base[it] - k * sz;
+                    double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        const double hk = th[k * SF_SD + m], dk = tdh[k * SF_SD + m];
+                        g0 += hk * sB[o + m * sz];
+                        g1 += hk * sB[SC + o + m * sz];
+                        g2 += dk * sB[2 * SC + o + m * sz];
+                    }
+                    g[it][a][0] = g0;
+                    g[it][a][1] = g1;
+                    g[it][a][2] = g2;
+                }
+            }
+        }
+        // ---- the point: physical gradient, flux, back to reference directions
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+            const int q = (sk[it] * P + sj[it]) * P + si[it];
+            const double *gp = geo + ((e0 + sel[it]) * nq + q) * G1;
+            const double c = gp[0];
+            double Ji[DIM][DIM];
+#pragma unroll
+            for (int b = 0; b < DIM; ++b)
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) Ji[b][k] = gp[1 + b * DIM + k];
+            double G[DIM][DIM], F[DIM][DIM];
+#pragma unroll
+            for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                for (int b = 0; b < DIM; ++b) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < DIM; ++k) s += Ji[b][k] * g[it][a][k];
+                    G[a][b] = s;
+                }
+            if (rule == 0) {
+#pragma unroll
+                for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                    for (int b = 0; b < DIM; ++b) F[a][b] = c * G[a][b];
+            } else {
+                double div = G[0][0];
+#pragma unroll
+                for (int a = 1; a < DIM; ++a) div += G[a][a];
+                const double cd = c * (SF_ALPHA_D * div);
+#pragma unroll
+                for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                    for (int b = 0; b < DIM; ++b) F[a][b] = a == b ? cd : c * (SF_ALPHA_W * (G[a][b] - G[b][a]));
+            }
+#pragma unroll
+            for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int b = 0; b < DIM; ++b) s += Ji[b][k] * F[a][b];
+                    g[it][a][k] = s;
+                }
+        }
+        __syncthreads();  // the last component's reads of sB (3-D)
+        // ---- transposed passes, per component
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) sB[k * SC + base[it]] = g[it][a][k];
+            }
+            __syncthreads();
+            if constexpr (DIM == 3) {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int k = sk[it], o = base[it] - k * sz;
+                    double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+                    for (int m = 0; m < P; ++m) {
+                        const double hk = th[m * SF_SD + k], dk = tdh[m * SF_SD + k];
+                        c0 += hk * sB[o + m * sz];
+                        c1 += hk * sB[SC + o + m * sz];
+                        c2 += dk * sB[2 * SC + o + m * sz];
+                    }
+                    sC[base[it]] = c0;
+                    sC[SC + base[it]] = c1;
+                    sC[2 * SC + base[it]] = c2;
+                }
+                __syncthreads();
+            }
+            const double *sY = DIM == 3 ? sC : sB;  // the y pass's input: (d/dx, d/dy[, h h d/dz]) parts
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int j = sj[it], o = base[it] - j * sy;
+                double d0 = 0.0, d1 = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    const double hj = th[m * SF_SD + j], dj = tdh[m * SF_SD + j];
+                    d0 += hj * sY[o + m * sy];
+                    d1 += dj * sY[SC + o + m * sy];
+                    if constexpr (DIM == 3) d1 += hj * sY[2 * SC + o + m * sy];
+                }
+                sA[base[it]] = d0;
+                sA[SC + base[it]] = d1;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!ok[it]) continue;
+                const int i = si[it], o = base[it] - i;
+                double s = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    s += tdh[m * SF_SD + i] * sA[o + m];
+                    s += th[m * SF_SD + i] * sA[SC + o + m];
+                }
+                res[it][a] = rule ? res[it][a] + s : s;
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        if (!ok[it]) continue;
+        double *out = ws + (t0 + tid + it * 256) * DIM;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) out[a] = negate ? -res[it][a] : res[it][a];
+    }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_gather(int64_t N, const int32_t *__restrict__ incp,
+                                                       const int32_t *__restrict__ inc,
+                                                       const uint8_t *__restrict__ dir, const double *__restrict__ ws,
+                                                       const double *__restrict__ x, double *__restrict__ y,
+                                                       const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    if (dir[node]) {
+        y[i] = x[i];  // setIndices2One: the unit Dirichlet diagonal of K and of Krhs
+        return;
+    }
+    double s = 0.0;
+    const int j1 = incp[node + 1];
+    for (int j = incp[node]; j < j1; ++j) s += ws[(int64_t)inc[j] * DIM + a];
+    y[i] = s;
+}
+
+// the diagonal of K_e per (element, node), into ws[e][l][a]
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_diag(int ngl, int nn, int64_t E, const double *__restrict__ tab,
+                                                     const double *__restrict__ geoF, const double *__restrict__ geoR,
+                                                     double *__restrict__ ws)
+{
+    constexpr int G1 = 1 + DIM * DIM;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= E * nn) return;
+    const int64_t e = t / nn;
+    const int l = (int)(t - e * nn);
+    const int li[3] = {l % ngl, (l / ngl) % ngl, DIM == 3 ? l / (ngl * ngl) : 0};
+    double sF = 0.0, sR[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) sR[a] = 0.0;
+    for (int rule = 0; rule < 2; ++rule) {
+        const int P = rule ? ngl - 1 : ngl;
+        const double *th = tab + rule * 128, *tdh = th + 64;
+        const int nq = DIM == 3 ? P * P * P : P * P;
+        const double *geo = (rule ? geoR : geoF) + e * nq * G1;
+        for (int q = 0; q < nq; ++q) {
+            const int qi[3] = {q % P, (q / P) % P, DIM == 3 ? q / (P * P) : 0};
+            double hh[DIM], dd[DIM], dref[DIM], gr[DIM];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) {
+                hh[d] = th[qi[d] * ngl + li[d]];
+                dd[d] = tdh[qi[d] * ngl + li[d]];
+            }
+            if constexpr (DIM == 2) {
+                dref[0] = dd[0] * hh[1];
+                dref[1] = hh[0] * dd[1];
+            } else {
+                dref[0] = dd[0] * hh[1] * hh[2];
+                dref[1] = hh[0] * dd[1] * hh[2];
+                dref[2] = hh[0] * hh[1] * dd[2];
+            }
+            const double *gp = geo + q * G1;
+            double n2 = 0.0;
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) s += gp[1 + i * DIM + k] * dref[k];
+                gr[i] = s;
+                n2 += s * s;
+            }
+            if (rule == 0) {
+                sF += gp[0] * n2;
+            } else {
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) {
+                    const double ga = gr[a] * gr[a];
+                    sR[a] += gp[0] * (SF_ALPHA_D * ga + SF_ALPHA_W * (n2 - ga));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) ws[t * DIM + a] = sF + sR[a];
+}
+
+// diagonal: the incident elements' entries in gather order (K), 0 (Krhs: a
+// free row holds Dirichlet columns only); 1 on Dirichlet rows
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_diag_gather(int64_t N, int which, const int32_t *__restrict__ incp,
+                                                            const int32_t *__restrict__ inc,
+                                                            const uint8_t *__restrict__ dir,
+                                                            const double *__restrict__ ws, double *__restrict__ d)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    if (dir[node]) {
+        d[i] = 1.0;
+        return;
+    }
+    double s = 0.0;
+    if (which == 0) {
+        const int j1 = incp[node + 1];
+        for (int j = incp[node]; j < j1; ++j) s += ws[(int64_t)inc[j] * DIM + a];
+    }
+    d[i] = s;
+}
+
+template <int DIM>
+static void launch_sumfac(const SumfacOp *P, hipStream_t st, const double *x, double *y, const int *istate)
+{
+    const unsigned ge = (unsigned)((P->E + P->neb - 1) / P->neb), gn = (unsigned)((P->N * DIM + 255) / 256);
+    hipLaunchKernelGGL(k_sumfac_elem<DIM>, dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se, P->E,
+                       P->negate, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate);
+    hipLaunchKernelGGL(k_sumfac_gather<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir, P->d_ws,
+                       x, y, istate);
+}
+
+int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
+{
+    const SumfacOp *P = A->sumfac;
+    if (!P) return fail(KLE_ERR_STATE, "sum-factorised operator without tables");
+    KLE_TRY(elem_check_vecs(A, x, y, "sum-factorised operator"));
+    if (P->dim == 2) launch_sumfac<2>(P, A->ctx->stream, x->d, y->d, istate);
+    else launch_sumfac<3>(P, A->ctx->stream, x->d, y->d, istate);
+    KLE_HIP(hipGetLastError());
+    return 0;
+}
+
+int sumfac_diagonal(const kle_mat *A, kle_vec *d)
+{
+    const SumfacOp *P = A->sumfac;
+    if (!P || !P->d_diag) return fail(KLE_ERR_STATE, "sum-factorised operator without tables");
+    hipStream_t st = A->ctx->stream;
+    KLE_HIP(hipMemcpyAsync(d->d, P->d_diag, sizeof(double) * (size_t)P->N * P->dim, hipMemcpyDeviceToDevice, st));
+    KLE_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+void sumfac_drop(kle_mat *A)
+{
+    SumfacOp *P = A->sumfac;
+    if (!P) return;
+    (void)hipFree(P->d_tab);
+    (void)hipFree(P->d_geoF);
+    (void)hipFree(P->d_geoR);
+    (void)hipFree(P->d_ws);
+    (void)hipFree(P->d_diag);
+    (void)hipFree(P->d_conn);
+    (void)hipFree(P->d_incp);
+    (void)hipFree(P->d_inc);
+    (void)hipFree(P->d_dir);
+    delete P;
+    A->sumfac = nullptr;
+}
+
+static int64_t sf_ipow(int b, int d) { return d == 2 ? (int64_t)b * b : (int64_t)b * b * b; }
+
+// Algorithmic bytes of one product.  k_sumfac_elem: the connectivity (4 E nn),
+// both geometry tables (8 E (nqF + nqR) (1 + dim^2)), the 1-D tables, x read
+// once (8 n), the element results written (8 E nn dim).  k_sumfac_gather: the
+// incidence list (4 (N + 1) + 4 E nn), the Dirichlet flags (N), the element
+// results read, y written (8 m).
+double sumfac_spmv_bytes(const kle_mat *A)
+{
+    const SumfacOp *P = A->sumfac;
+    if (!P) return 0.0;
+    const double nq = (double)(sf_ipow(P->npF, P->dim) + sf_ipow(P->npR, P->dim));
+    return 4.0 * P->E * P->nn + 8.0 * P->E * nq * (1 + P->dim * P->dim) + 8.0 * 4 * P->ngl * P->ngl + 8.0 * A->n_local +
+           2.0 * 8.0 * P->E * P->nn * P->dim + 4.0 * (P->N + 1) + 4.0 * P->ninc + 1.0 * P->N + 8.0 * A->m_local;
+}
+
+std::string sumfac_kernel_name(const kle_mat *A)
+{
+    const SumfacOp *P = A->sumfac;
+    if (!P) return "?";
+    const std::string d = std::to_string(P->dim);
+    return "k_sumfac_elem<" + d + ">+k_sumfac_gather<" + d + ">";
+}
+
+// Every index the device tables hold, checked on the host before upload: a
+// bad table is an error code, never an out-of-range access.  conn [E][nn]
+// (unmasked) names nodes in [0, N); node i's incidence entries
+// inc[incp[i] .. incp[i + 1]) are positions of conn that name i, their
+// elements strictly ascending, and together they cover conn.
+int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &incp,
+                    const std::vector<int32_t> &inc, int64_t E, int64_t N, int nn, int dim)
+{
+    if (E < 1 || N < 1 || nn < 1) return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: empty mesh");
+    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
+    if ((int64_t)conn.size() != E * nn || (int64_t)incp.size() != N + 1 || (int64_t)inc.size() != E * nn)
+        return fail(KLE_ERR_SIZ, "sum-factorised operator: table sizes do not match the mesh");
+    for (int64_t k = 0; k < E * nn; ++k)
+        if (conn[k] < 0 || conn[k] >= N)
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld = %d outside [0, %lld)",
+                        (long long)k, conn[k], (long long)N);
+    if (incp[0] != 0 || incp[N] != E * nn)
+        return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: the incidence list does not cover the connectivity");
+    for (int64_t i = 0; i < N; ++i) {
+        if (incp[i + 1] < incp[i] || incp[i + 1] > E * nn)
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: incidence offsets of node %lld descend", (long long)i);
+        int64_t prev = -1;
+        for (int32_t j = incp[i]; j < incp[i + 1]; ++j) {
+            const int32_t t = inc[j];
+            if (t < 0 || (int64_t)t >= E * nn || conn[t] != i || t / nn <= prev)
+                return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: incidence entry %d of node %lld is inconsistent",
+                            j - incp[i], (long long)i);
+            prev = t / nn;
+        }
+    }
+    return 0;
+}
+
+}  // namespace kle
+
+using namespace kle;
+
+extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which >= 0 && which <= 2, "which must be 0 (K) or 1 (Krhs)");
+    if (which == 2) return fail(KLE_ERR_SUP, "sum-factorised operator: Rw has no sum-factorised form here");
+    if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "sum-factorised operator: no-slip meshes are not supported");
+    if (m->nranks != ctx->nranks)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
+                    m->nranks, ctx->nranks);
+    if (m->nranks > 1) return fail(KLE_ERR_SUP, "sum-factorised operator: one rank only");
+    const int dim = m->dim, ngl = m->ngl, nn = m->nn(), G1 = 1 + dim * dim;
+    KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "sum-factorised operator: dim 2 or 3, ngl 2..8");
+    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+    ElemLayout L;
+    L.N = L.next = m->node_end - m->node_begin;
+    L.E = L.eint1 = m->n_local_elems();
+    const int64_t E = L.E, N = L.N;
+    KLE_ARG(E >= 1 && N >= 1 && m->node_begin == 0 && m->ext_begin == 0 && m->ext_end == N && N == m->N,
+            "unexpected one-rank layout");
+    if ((int64_t)m->dir.size() != N) return fail(KLE_ERR_SIZ, "sum-factorised operator: Dirichlet flags do not match the mesh");
+    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
+
+    // tables (host), validated before upload
+    std::vector<int64_t> conn64((size_t)E * nn);
+    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
+    std::vector<int32_t> conn((size_t)E * nn), incp((size_t)N + 1, 0), inc((size_t)E * nn, -1);
+    for (int64_t k = 0; k < E * nn; ++k) {
+        if (conn64[k] < 0 || conn64[k] >= N)
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld outside the mesh", (long long)k);
+        conn[k] = (int32_t)conn64[k];
+        ++incp[conn[k] + 1];
+    }
+    for (int64_t i = 0; i < N; ++i) incp[i + 1] += incp[i];
+    {
+        std::vector<int32_t> fill(incp.begin(), incp.end() - 1);
+        for (int64_t k = 0; k < E * nn; ++k) inc[fill[conn[k]]++] = (int32_t)k;  // k = e * nn + l, ascending e
+    }
+    KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, dim));
+    // the mask rule folded into the connectivity the element kernel reads: K
+    // drops the Dirichlet entries of x, Krhs the free ones
+    for (int64_t k = 0; k < E * nn; ++k)
+        if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
+
+    // LDS layout: odd strides (in doubles) of the y lines, z planes and elements
+    // (a workgroup's only element needs no element stride), as kle_colloc.hip
+    const int neb = std::max(1, 256 / nn);
+    const int sy = ngl | 1, sz = dim == 3 ? (ngl * sy) | 1 : 0, se = ngl * (dim == 3 ? sz : sy) | (neb > 1 ? 1 : 0);
+    if ((int64_t)neb * se > (dim == 3 ? SF_SC3 : SF_SC2) || (int64_t)neb * nn > (dim == 3 ? 512 : 256))
+        return fail(KLE_ERR_STATE, "sum-factorised operator: %d elements of stride %d exceed the LDS tile", neb, se);
+
+    // the 1-D tables of kle_basis, [q][a]
+    PointSet1D full, red, op;
+    element_sets(ngl, full, red, op);
+    const int npF = (int)full.x.size(), npR = (int)red.x.size();
+    if (npF != ngl || npR != ngl - 1 || (int)full.h.size() != npF * ngl || (int)red.dh.size() != npR * ngl)
+        return fail(KLE_ERR_STATE, "sum-factorised operator: unexpected quadrature rules");
+    std::vector<double> tab(256, 0.0);
+    std::copy(full.h.begin(), full.h.end(), tab.begin());
+    std::copy(full.dh.begin(), full.dh.end(), tab.begin() + 64);
+    std::copy(red.h.begin(), red.h.end(), tab.begin() + 128);
+    std::copy(red.dh.begin(), red.dh.end(), tab.begin() + 192);
+
+    KLE_HIP(hipSetDevice(ctx->device));
+    kle_mat *A = new kle_mat;
+    SumfacOp *P = new SumfacOp;
+    A->ctx = ctx;
+    A->sumfac = P;
+    elem_mat_fields(A, m, L, dim, dim);
+    P->which = which;
+    P->negate = which == 1;
+    P->dim = dim;
+    P->ngl = ngl;
+    P->nn = nn;
+    P->neb = neb;
+    P->sy = sy;
+    P->sz = sz;
+    P->se = se;
+    P->npF = npF;
+    P->npR = npR;
+    P->E = E;
+    P->N = N;
+    P->ninc = E * nn;
+    auto up = [&](auto **dp, const void *src, size_t bytes) {
+        if (hipMalloc(dp, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *dp = nullptr;
+            return fail(KLE_ERR_MEM, "out of device memory for the sum-factorised operator");
+        }
+        return src ? h2d(*dp, src, bytes) : 0;
+    };
+    // c_q and inv J of every element at both rules' points: the assembly's own
+    // geometry kernel on the mesh's own corners
+    int gpF = 0, gpR = 0;
+    int rc = element_geometry(ctx, m, &P->d_geoF, &P->d_geoR, &gpF, &gpR);
+    if (!rc && (gpF != npF || gpR != npR)) rc = fail(KLE_ERR_STATE, "sum-factorised operator: geometry tables do not match the rules");
+    if (!rc) rc = up(&P->d_tab, tab.data(), sizeof(double) * tab.size());
+    if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
+    if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
+    if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);
+    if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * dim);
+    if (!rc) rc = up(&P->d_diag, nullptr, sizeof(double) * (size_t)N * dim);
+    if (!rc) {
+        // the diagonal, once: element entries into ws, gathered like a product
+        const unsigned ge = (unsigned)((E * nn + 255) / 256), gn = (unsigned)((N * dim + 255) / 256);
+        hipStream_t st = ctx->stream;
+        if (dim == 2) {
+            if (which == 0)
+                hipLaunchKernelGGL(k_sumfac_diag<2>, dim3(ge), dim3(256), 0, st, ngl, nn, E, P->d_tab, P->d_geoF,
+                                   P->d_geoR, P->d_ws);
+            hipLaunchKernelGGL(k_sumfac_diag_gather<2>, dim3(gn), dim3(256), 0, st, N, which, P->d_incp, P->d_inc,
+                               P->d_dir, P->d_ws, P->d_diag);
+        } else {
+            if (which == 0)
+                hipLaunchKernelGGL(k_sumfac_diag<3>, dim3(ge), dim3(256), 0, st, ngl, nn, E, P->d_tab, P->d_geoF,
+                                   P->d_geoR, P->d_ws);
+            hipLaunchKernelGGL(k_sumfac_diag_gather<3>, dim3(gn), dim3(256), 0, st, N, which, P->d_incp, P->d_inc,
+                               P->d_dir, P->d_ws, P->d_diag);
+        }
+        hipError_t he = hipGetLastError();
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he != hipSuccess) rc = fail(KLE_ERR_DEVICE, "sum-factorised operator: diagonal kernels: %s", hipGetErrorString(he));
+    }
+    if (rc) {
+        kle_mat_destroy(A);
+        return rc;
+    }
+    *out = A;
+    return 0;
+}

@@ -131,6 +131,20 @@ class MatFS:
             self._elemRw = Mat.createKLEElement(self.dom.getMesh(), "Rw")
         return self._elemRw
 
+    def getSumFactoredK(self):
+        """K as a sum-factorised element-wise operator
+        (Mat.createKLESumFactored): no assembled values and no element matrix,
+        any one-rank mesh (box or unstructured).  Created on first use."""
+        if getattr(self, "_sumfacK", None) is None:
+            self._sumfacK = Mat.createKLESumFactored(self.dom.getMesh(), "K")
+        return self._sumfacK
+
+    def getSumFactoredKrhs(self):
+        """Krhs as a sum-factorised element-wise operator; created on first use."""
+        if getattr(self, "_sumfacKrhs", None) is None:
+            self._sumfacKrhs = Mat.createKLESumFactored(self.dom.getMesh(), "Krhs")
+        return self._sumfacKrhs
+
     def buildOperators(self, opType=None):
         """Curl / SrT / DivSrT on the device (mat_fs.py:194-201): assembled
         whatever the kleType, unless opType (default: -kle_op_type) is

@@ -406,6 +406,29 @@ class Mat:
         m.setName("element " + which)
         return m
 
+    @classmethod
+    def createKLESumFactored(cls, mesh, which="K"):
+        """Sum-factorised element-wise K or Krhs of any one-rank mesh, uniform
+        box or unstructured (kle_mat_create_kle_sumfac): the product is a
+        quadrature-point evaluation with per-point geometry -- 1-D passes with
+        the basis tables, c_q and inv J from the tables the assembly's geometry
+        kernel fills -- and reads neither assembled values nor an element
+        matrix.  mult, *, multAdd, createVecLeft/Right, getDiagonal, the size
+        getters, getInfo, spmvKernel, timeLocalSpmv and KSP.setOperators work
+        as on createKLEElement's operators; calls that need stored values and
+        copyDirichletRows raise Error 56, as do which="Rw", no-slip meshes,
+        several ranks and a mesh partitioned for another rank count than the
+        context's; any other `which` raises Error 62."""
+        kinds = {"K": 0, "Krhs": 1, "Rw": 2}
+        if which not in kinds:
+            raise Error(62, f"createKLESumFactored: which must be 'K' or 'Krhs', not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_kle_sumfac", ctx.h, mesh._h, kinds[which], C.byref(h))
+        m = cls._wrap(h, ctx, mesh, mesh.dim, mesh.dim)
+        m.setName("sum-factorised " + which)
+        return m
+
     def copyDirichletRows(self, src, dst):
         """dst[i] = src[i] on the Dirichlet rows of an element-wise operator,
         nothing else touched (kle_mat_copy_dirichlet_rows)."""

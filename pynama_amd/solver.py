@@ -35,7 +35,7 @@ class KleSolver:
     def __init__(self):
         self.mat = None
         self._b = None
-        self._Krhs = self._Rw = None  # the element-wise Krhs and Rw with -kle_k_type element
+        self._Krhs = self._Rw = None  # the element-wise Krhs and Rw with -kle_k_type element (sumfac: Krhs)
         self._exactBC = False
 
     def setMat(self, mat):
@@ -48,15 +48,21 @@ class KleSolver:
         # getElementRw); whatever they refuse (unstructured, no-slip) raises --
         # no fallback.  After a matrix-free build
         # (-kle_mat_type element) mat.K, mat.Krhs and mat.Rw are those already.
+        # -kle_k_type sumfac: the KSP's operator and rhs()'s Krhs are the
+        # sum-factorised operators (MatFS.getSumFactoredK / getSumFactoredKrhs:
+        # any one-rank mesh, unstructured included); Rw stays mat.Rw.
         ktype = Options().getString("kle_k_type", "assembled")
-        if ktype not in ("assembled", "element"):
-            raise Error(62, f"-kle_k_type {ktype}: assembled | element")
+        if ktype not in ("assembled", "element", "sumfac"):
+            raise Error(62, f"-kle_k_type {ktype}: assembled | element | sumfac")
         self._Krhs = self.mat.getElementKrhs() if ktype == "element" else None
         self._Rw = self.mat.getElementRw() if ktype == "element" else None
+        if ktype == "sumfac":
+            self._Krhs = self.mat.getSumFactoredKrhs()
         # matrix-free build: solve() hands back the Dirichlet values exactly
         self._exactBC = K.getFormat() == "elem"
         self.solver = KspSolver()
-        self.solver.createSolver(self.mat.getElementK() if ktype == "element" else K)
+        self.solver.createSolver(self.mat.getElementK() if ktype == "element"
+                                 else self.mat.getSumFactoredK() if ktype == "sumfac" else K)
         self.__vel = K.createVecRight()
         self.__vel.setName("velocity")
         self._b = K.createVecLeft()

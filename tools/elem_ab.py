@@ -66,8 +66,28 @@ on which it can, named in every record), in one process:
   solve_ns      one solveFS + solve from the element build (wall time,
                 iterations, reasons)
 
+With --sumfac the legs are those of the sum-factorised K
+(Mat.createKLESumFactored, kle_sumfac.hip; records to
+profiles/elem/sumfac.jsonl), in one process, legs alternating round by round:
+
+  (a) unstructured  the mesh bench.py --mesh unstructured generates
+                    (perturbed_box(3, nelem, seed=5) of the first mesh, written
+                    as a Gmsh file): K as the bench configures it (mat.build's
+                    defaults: symmetric storage, graph bricks) against the
+                    sum-factorised K -- --reps products and --its fixed
+                    iterations of classic Jacobi-CG on each
+  (b) box           the box mesh of the same size: the dense-GEMM element K
+                    (Mat.createKLEElement) against the sum-factorised K,
+                    --reps products
+
+each with the build wall time and the device memory held (hipMemGetInfo before
+/ after).  With --check: KleSolver.solve on Taylor-Green on (a) with the
+assembled and with the sum-factorised operators (-kle_k_type sumfac) to rtol
+1e-10, iterations and the true residual K u - (Rw w + Krhs u_bc) through the
+assembled matrices.
+
   python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
-                          [--matfree | --operators [--config4] | --noslip]
+                          [--matfree | --operators [--config4] | --noslip | --sumfac]
 """
 import argparse
 import ctypes as C
@@ -306,6 +326,118 @@ def matfree(a, pa, np, hip, ctx, emit):
             emit(dict(base, leg="check_solve_matfree",
                       **check_solve_matfree(pa, np, dom, mats["element"], mats["assembled"])))
         del ops, mats, x, y, dom
+        gc.collect()
+
+
+def sumfac(a, pa, np, hip, ctx, emit):
+    import tempfile
+
+    from pynama_amd.meshgen import perturbed_box, write_gmsh
+    from pynama_amd.petsc import Mat, Options
+    ne_s, ngl = a.meshes[0].split(":")
+    nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+    dim = len(nelem)
+    bc = {"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}}
+    path = os.path.join(tempfile.mkdtemp(prefix="kle_sumfac_"), "mesh.msh")
+    write_gmsh(path, dim, *perturbed_box(dim, nelem, seed=5))
+    domains = {"unstructured": {"ngl": ngl, "gmsh-file": path},
+               "box": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * dim, "upper": [1.0] * dim}}}
+
+    def timed_build(fn):
+        gc.collect()
+        ctx.synchronize()
+        m0, t0 = hip.free_bytes(), time.perf_counter()
+        out = fn()
+        ctx.synchronize()
+        return out, 1e3 * (time.perf_counter() - t0), m0 - hip.free_bytes()
+
+    for leg, domain in domains.items():
+        dom = pa.Domain()
+        dom.configure({"domain": domain, "boundary-conditions": bc})
+        dom.setUp()
+        base = {"mesh": leg, "nelem": nelem, "ngl": ngl, "dofs": dom.mesh.N * dim, "rounds": a.rounds}
+        mat = pa.MatFS()
+        mat.setDomain(dom)
+        _, t_asm, m_asm = timed_build(lambda: mat.build(buildOperators=False))
+        Ks, t_sf, m_sf = timed_build(lambda: Mat.createKLESumFactored(dom.mesh, "K"))
+        build = {"assembled": {"ms": t_asm, "device_bytes_K_Krhs_Rw": m_asm},
+                 "sumfac": {"ms": t_sf, "device_bytes_K": m_sf}}
+        if leg == "box":
+            Ke, t_el, m_el = timed_build(lambda: mat.getElementK())
+            build["element"] = {"ms": t_el, "device_bytes_K": m_el}
+            ops = {"element": Ke, "sumfac": Ks}
+        else:
+            ops = {"assembled": mat.K, "sumfac": Ks}
+        x = mat.K.createVecRight()
+        x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+        y = mat.K.createVecLeft()
+        b = mat.K.createVecLeft()
+        b.setArray(np.random.default_rng(2).uniform(-1, 1, b.getLocalSize()))
+        ksps = {}
+        if leg == "unstructured":
+            for label, A in ops.items():
+                ksp = pa.petsc.KSP().create()
+                ksp.setType("cg")
+                pc = pa.petsc.PC().create()
+                pc.setType("jacobi")
+                ksp.setPC(pc)
+                ksp.setCGSingleReduction(False)
+                ksp.setOperators(A)
+                ksp.setUp()
+                ksp.setFixedIterations(a.its)
+                ksps[label] = (ksp, A.createVecRight())
+        t_prod, t_cg = {k: [] for k in ops}, {k: [] for k in ksps}
+        for _ in range(a.rounds):
+            for label, A in ops.items():
+                for _w in range(20):
+                    A.mult(x, y)
+                ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                t_prod[label].append(1e3 * ms / a.reps)
+            for label, (ksp, u) in ksps.items():
+                u.set(0.0)
+                ksp.solve(b, u)  # warm-up: the same fixed iterations
+                u.set(0.0)
+                ms = hip.timed_ms(lambda: ksp.solve(b, u))
+                if ksp.getConvergedReason() < 0:
+                    raise SystemExit(f"elem_ab: the fixed CG iterations diverged ({label})")
+                t_cg[label].append(1e3 * ms / a.its)
+        for label, A in ops.items():
+            emit(dict(base, leg="product", operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(), reps=a.reps,
+                      us=spread(t_prod[label]), build=build[label]))
+        for label, (ksp, _u) in ksps.items():
+            emit(dict(base, leg="cg", operator=label, ksp="cg (classic) + jacobi", kernel=ops[label].spmvKernel(),
+                      iterations=a.its, us_per_iteration=spread(t_cg[label])))
+        other = "element" if leg == "box" else "assembled"
+        ratio = {"product": statistics.median(t_prod[other]) / statistics.median(t_prod["sumfac"])}
+        if ksps:
+            ratio["cg_iteration"] = statistics.median(t_cg[other]) / statistics.median(t_cg["sumfac"])
+        emit(dict(base, leg="ratio", **{other + "_over_sumfac": ratio}))
+        if a.check and leg == "unstructured":
+            f = pa.fields.get(bc["custom-func"]["name"])
+            for ktype in ("assembled", "sumfac"):
+                opts = Options()
+                opts.setValue("kle_k_type", ktype)
+                try:
+                    sol = pa.KleSolver()
+                    sol.setMat(mat)
+                    sol.setUp()
+                finally:
+                    opts.delValue("kle_k_type")
+                vort = mat.Rw.createVecRight()
+                vort.setArray(np.asarray(f.vorticity(dom.getFullCoordArray(), 1.0), dtype=np.float64).ravel())
+                vel = sol.getSolution()
+                dom.applyBoundaryConditions(vel, "velocity", 0.0, 0.02)
+                rhs = mat.Rw * vort
+                rhs.axpy(1.0, mat.Krhs * vel)  # vel holds u_bc on the Dirichlet nodes; Krhs reads nothing else
+                sol.solve(vort)
+                ksp = sol.getKSP()
+                r = mat.K * vel
+                r.aypx(-1.0, rhs)
+                emit(dict(base, leg="check_solve", k_type=ktype, operator=ksp.getOperators()[0].spmvKernel(),
+                          iterations=ksp.getIterationNumber(), reason=ksp.getConvergedReason(), rtol=1e-10,
+                          true_rel_residual_assembled=r.norm() / rhs.norm()))
+                del sol
+        del ksps, ops, Ks, mat, dom, x, y, b
         gc.collect()
 
 
@@ -696,13 +828,16 @@ def main():
                     help="with --operators: one evalRHS at [18,18,18] ngl 7 with nothing assembled, instead of the legs")
     ap.add_argument("--noslip", action="store_true",
                     help="the matrix-free no-slip legs on a six-wall lid-driven box at the first mesh")
+    ap.add_argument("--sumfac", action="store_true",
+                    help="the sum-factorised K: the first mesh as bench.py's unstructured mesh (vs the assembled K) "
+                         "and as a box (vs the dense-GEMM element K)")
     ap.add_argument("--fallback-meshes", nargs="*", default=["16,12,12:5", "12,10,10:5", "8,8,6:5"],
                     help="with --noslip: tried in order where the assembled no-slip set cannot be built")
     ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree, "
                                                 "operators.jsonl with --operators, noslip.jsonl with --noslip)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "elem", "noslip.jsonl" if a.noslip else
+        a.out = os.path.join(ROOT, "profiles", "elem", "sumfac.jsonl" if a.sumfac else "noslip.jsonl" if a.noslip else
                              "operators.jsonl" if a.operators else
                              "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
     import numpy as np
@@ -719,6 +854,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.sumfac:
+        sumfac(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     if a.noslip:
         noslip(a, pa, np, hip, ctx, emit)
         fout.close()
