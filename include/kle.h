@@ -108,7 +108,24 @@ const char *kle_last_error(void);
  * partial 64-block passes share one item; 1 default), "spmv_brick_singles"
  * (read at build: rows of one stored block -- the Dirichlet rows and the
  * free rows at the far corner of their box -- formed by the gather instead
- * of as items of the bricks; 1 default), "spmv_gather_wps" (the run-mask
+ * of as items of the bricks; 1 default), "spmv_brick_dedup" (read at build:
+ * bricked rows whose value streams are bitwise equal -- a box-mesh K repeats
+ * a few distinct rows over the lattice -- are stored once; proposed by a
+ * hash, decided by comparison, kept only where it saves at least half of the
+ * bricked bytes and fits the descriptors' 1 GiB; the product is bitwise the
+ * same; 1 default, 0 every row's own stream), "spmv_brick_dedup_nt" (value
+ * loads of a deduplicated K: 0 default plain cached, 1 nontemporal as the
+ * full stream's), "spmv_brick_dedup_full" (read at build: a K whose rows are
+ * shared keeps the full 9-entry blocks -- read from the caches, the kernel is
+ * bound by its instructions and the compact stream's offsets cost more than
+ * its bytes save; the full layout is built first and the compact one only
+ * where the sharing is not taken; 1 default, 0 the compact stream first),
+ * "asm_box_uniform" (read at assembly: on a box mesh every cell adds the
+ * blocks of global element 0's K_e and Rw_e into the free-slip K, Krhs and
+ * Rw, so rows that are translates of each other are the same bits and the
+ * brick SpMV stores them once; the values move by coordinate rounding,
+ * <= 1e-12 of the largest entry; 1 default, 0 each cell's own matrix),
+ * "spmv_gather_wps" (the run-mask
  * gather's waves per 64-row slice: 1, 2, 4; 0 default, by the runs per
  * slice), "elem_ghost_rows" (element-wise K, Krhs, Rw on several ranks: the
  * ghost layer's GEMM over the row groups holding its top-plane rows alone;
@@ -213,6 +230,16 @@ int kle_ctx_get_comm_info(kle_ctx *ctx, int *count, int *rank);
  * carry a block. */
 int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int rounds, int split, int *info,
                        double *stats);
+/* Diagnostic, host only: that plan with its value offsets rewritten as the
+ * row dedup of the brick SpMV ("spmv_brick_dedup") rewrites them -- rows with
+ * equal packed boxes share the first one's values, every brick's base is 0 --
+ * and checked against the unique array by the validator every brick product
+ * passes before its first launch.  shift > 0 moves the last row's offset
+ * that many 16-double units on, out of the array: refused (KLE_ERR_SUP).
+ * shift -1 gives the last brick a value base of its own inside a longer
+ * array: refused too (shared values have one common base, 0).
+ * out[3]: rows in bricks, rows stored, doubles of the unique array. */
+int kle_brick_plan_box_shared(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int shift, long long *out);
 /* Per-kernel HIP-event timing of the hot kernels (SpMV, CG updates). */
 int kle_ctx_set_profiling(kle_ctx *ctx, int on);
 /* Time only the launches tagged `name` ("spmv", "dot", "cg_update", "reduce",
@@ -682,6 +709,11 @@ int kle_mat_get_sym_bricks(const kle_mat *A, int *nbricks, int *dims, double *en
  * are all stored as +0.0 streams the other entries alone) and how many entries
  * it leaves out; 0, 0 otherwise. */
 int kle_mat_get_brick_compact(const kle_mat *A, int *compact, long long *dropped_entries);
+/* Whether the bricks' rows with bitwise equal value streams share one copy
+ * (tuning "spmv_brick_dedup"), and then the rows stored and their bytes
+ * (each row padded to 16 doubles); 0, 0, 0 otherwise.  kle_mat_spmv_bytes
+ * still counts what the kernel's loads request, not what reaches HBM. */
+int kle_mat_get_brick_dedup(const kle_mat *A, int *dedup, long long *unique_rows, long long *unique_bytes);
 /* N > 1: run the rows that read no ghost entry while the halo exchange is in
  * flight on a second stream (default on). */
 int kle_mat_set_halo_overlap(kle_mat *A, int on);

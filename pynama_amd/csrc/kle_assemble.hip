@@ -532,13 +532,19 @@ __host__ __device__ inline bool box_zero_entry(const int64_t ci[3], const int64_
 // MODE 0: K (free cols, +K_e), 1: Krhs (Dirichlet cols, -K_e), 2: Rw (+Rw_e)
 // zrule (MODE 0, 3 x 3 blocks): the entries under box_zero_entry are stored
 // as +0.0 (tuning asm_box_zeros)
+// uni (tuning asm_box_uniform): Eblk holds one element matrix, global element
+// 0's, and every cell adds its blocks -- on a box mesh all elements are the
+// same brick, so rows that are translates of each other come out as the same
+// bits (coordinate rounding made them differ in the last places) and the
+// brick SpMV stores them once (kle_brick.hip brick_dedup).  The cells and
+// their order are unchanged.
 template <int R, int C, int MODE>
 __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const int *__restrict__ rowptr,
                                                 const int *__restrict__ rowcnt, const int64_t *__restrict__ vptr,
                                                 int lay, const int *__restrict__ bcol,
                                                 const uint8_t *__restrict__ dir,
                                                 const double *__restrict__ Eblk, double *__restrict__ val,
-                                                int64_t eb0, int64_t eb1, int accum, int zrule)
+                                                int64_t eb0, int64_t eb1, int accum, int zrule, int uni)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -595,12 +601,13 @@ __global__ __launch_bounds__(256) void k_gather(MeshDev M, int64_t nrows, const 
                     if (!in || e < eb0 || e >= eb1) continue;
                     const int li = oi[0] + ngl * (oi[1] + ngl * oi[2]);
                     const int lj = oj[0] + ngl * (oj[1] + ngl * oj[2]);
+                    const int64_t es = uni ? 0 : e - eb0;
                     if constexpr (MODE == 0 && R == C) {
-                        const double *Ee = Eblk + (e - eb0) * ne * (int64_t)ne * (R * C);
+                        const double *Ee = Eblk + es * ne * (int64_t)ne * (R * C);
 #pragma unroll
                         for (int t = 0; t < R * C; ++t) acc[t] += sym_elem_entry<R, C>(Ee, ne, li, lj, t);
                     } else {
-                        const double *blk = Eblk + (((e - eb0) * ne + li) * (int64_t)ne + lj) * (R * C);
+                        const double *blk = Eblk + ((es * ne + li) * (int64_t)ne + lj) * (R * C);
 #pragma unroll
                         for (int t = 0; t < R * C; ++t) acc[t] += (MODE == 1) ? -blk[t] : blk[t];
                     }
@@ -1666,12 +1673,12 @@ static void launch_gather_ns(kle_ctx *ctx, const MeshDev &M, kle_mat *A, const u
 
 template <int R, int C, int MODE>
 static void launch_gather(kle_ctx *ctx, const MeshDev &M, kle_mat *A, const uint8_t *dir, const double *E,
-                          int64_t eb0 = 0, int64_t eb1 = INT64_MAX, int accum = 0)
+                          int64_t eb0 = 0, int64_t eb1 = INT64_MAX, int accum = 0, int uni = 0)
 {
     const int64_t threads = A->nrows * 64;
     hipLaunchKernelGGL((k_gather<R, C, MODE>), dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, M,
                        A->nrows, A->d_rowptr, A->d_rowcnt, A->d_vptr, A->vlayout, A->d_bcol, dir, E, A->d_val,
-                       eb0, eb1, accum, (MODE == 0 && M.dim == 3 && g_tune.asm_box_zeros) ? 1 : 0);
+                       eb0, eb1, accum, (MODE == 0 && M.dim == 3 && g_tune.asm_box_zeros) ? 1 : 0, uni);
 }
 
 // ------------------------------------------------------- unstructured
@@ -2098,12 +2105,14 @@ int kle_assemble_kle(kle_ctx *ctx, kle_mesh *m, kle_mat **K, kle_mat **Krhs, kle
     const int64_t nbatch = (nel + nb - 1) / nb;
     const int accum = nbatch > 1;
     struct Scratch {
-        double *ke = nullptr, *rw = nullptr;
+        double *ke = nullptr, *rw = nullptr, *ke0 = nullptr, *rw0 = nullptr;
         uint8_t *dir = nullptr;
         ~Scratch()
         {
             if (ke) (void)hipFree(ke);
             if (rw) (void)hipFree(rw);
+            if (ke0) (void)hipFree(ke0);
+            if (rw0) (void)hipFree(rw0);
             if (dir) (void)hipFree(dir);
         }
     } sc;
@@ -2117,9 +2126,21 @@ int kle_assemble_kle(kle_ctx *ctx, kle_mesh *m, kle_mat **K, kle_mat **Krhs, kle
             KLE_HIP(hipMemsetAsync(A->d_val, 0, sizeof(double) * std::max<int64_t>(A->nvals, 1), ctx->stream));
     MeshDev M = mesh_dev(m);
     const uint8_t *ddir = sc.dir;
+    // asm_box_uniform: the matrices of global element 0, formed from the same
+    // corners on every rank (kle_elem.hip first_element_mesh), so a rank's
+    // owned rows do not depend on the partition
+    const int uni = m->kind == 0 && g_tune.asm_box_uniform && nel > 0;
+    if (uni) {
+        kle_mesh m0;
+        first_element_mesh(m, &m0);
+        KLE_TRY(element_first_k(ctx, &m0, &sc.ke0, &sc.rw0));
+    }
     tm.lap("assemble_kle: geometry + scratch");
     for (int64_t e0 = 0; e0 < std::max<int64_t>(nel, 1); e0 += nb) {
         const int64_t cnt = std::min(nb, nel - e0), e1 = e0 + std::max<int64_t>(cnt, 0);
+        // (uni: the gathers below read ke0 / rw0 alone, so what this batch
+        // writes to sc.ke and sc.rw is read by nobody; it is still computed --
+        // leaving it and its scratch out changes the batching and is not done here)
         KLE_TRY(element_batch(ctx, m, S, e0, cnt, sc.ke, sc.rw, nullptr));
         if (m->kind == 1) {
             if (dim == 3) {
@@ -2132,13 +2153,13 @@ int kle_assemble_kle(kle_ctx *ctx, kle_mesh *m, kle_mat **K, kle_mat **Krhs, kle
                 launch_gather_u<2, 1, 2>(ctx, U.dev, mRw, ddir, nullptr, sc.rw, e0, e1, accum);
             }
         } else if (dim == 3) {
-            launch_gather<3, 3, 0>(ctx, M, mK, ddir, sc.ke, e0, e1, accum);
-            launch_gather<3, 3, 1>(ctx, M, mKr, ddir, sc.ke, e0, e1, accum);
-            launch_gather<3, 3, 2>(ctx, M, mRw, ddir, sc.rw, e0, e1, accum);
+            launch_gather<3, 3, 0>(ctx, M, mK, ddir, uni ? sc.ke0 : sc.ke, e0, e1, accum, uni);
+            launch_gather<3, 3, 1>(ctx, M, mKr, ddir, uni ? sc.ke0 : sc.ke, e0, e1, accum, uni);
+            launch_gather<3, 3, 2>(ctx, M, mRw, ddir, uni ? sc.rw0 : sc.rw, e0, e1, accum, uni);
         } else {
-            launch_gather<2, 2, 0>(ctx, M, mK, ddir, sc.ke, e0, e1, accum);
-            launch_gather<2, 2, 1>(ctx, M, mKr, ddir, sc.ke, e0, e1, accum);
-            launch_gather<2, 1, 2>(ctx, M, mRw, ddir, sc.rw, e0, e1, accum);
+            launch_gather<2, 2, 0>(ctx, M, mK, ddir, uni ? sc.ke0 : sc.ke, e0, e1, accum, uni);
+            launch_gather<2, 2, 1>(ctx, M, mKr, ddir, uni ? sc.ke0 : sc.ke, e0, e1, accum, uni);
+            launch_gather<2, 1, 2>(ctx, M, mRw, ddir, uni ? sc.rw0 : sc.rw, e0, e1, accum, uni);
         }
         KLE_HIP(hipGetLastError());
     }

@@ -87,7 +87,15 @@ constexpr int BI_NEWP = 1024;  // (sf: the item starts row P -- its x into the r
 // partial pass first, as the shared item reads it before the full passes).
 // A lane whose slot is left out loads its part's first value (a line an
 // active lane of the same load reads) and takes 0.0 after the wait.
-template <int WV, bool FF = true, bool DOT = false, bool CP = false>
+// DD: a deduplicated value array (brick_dedup, below): rows with bitwise
+// equal streams share one copy, so the two rows of an item may lie anywhere
+// in the array, the second before the first.  The loads' scalar base is then
+// the array itself and each lane's 32-bit offset starts at its own row's
+// place in it (below 2^30 bytes: 23 bits x 16 doubles), instead of row P's
+// address and the distance from P to Q.  NTL: nontemporal value loads (the
+// full stream is read once per product; a deduplicated one is re-read by
+// every brick and may stay cached).
+template <int WV, bool FF = true, bool DOT = false, bool CP = false, bool DD = false, bool NTL = true>
 __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly, int Lz, int zo, int hp, int rstride,
                                                                  const BrickDesc *__restrict__ bd,
                                                                  const int2 *__restrict__ rowd,
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         const int mu = q ? Q.mu : P.mu;
         const int kraw = q ? kbQ + lane - s : kbP + lane;
         const int kk = min(kraw, mu - 1);
-        const unsigned bo = q ? (unsigned)(Q.v - P.v) * 8u : 0u;
+        const unsigned bo = DD ? (unsigned)((q ? Q.v : P.v) - vb) * 8u : q ? (unsigned)(Q.v - P.v) * 8u : 0u;
         const int k = (q ? Q.k0 : P.k0) + kk;
         const int bnxy = q ? Q.bnxy : P.bnxy, bnx = q ? Q.bnx : P.bnx;
         const int kz = sym_div(k, bnxy, __builtin_amdgcn_rcpf((float)bnxy)), rem = k - kz * bnxy;
@@ -264,10 +272,10 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
             rr |= db << 16;
         }
         // (the base is wave-uniform; said so, as the loads take it in SGPRs)
-        const unsigned long long pb = (unsigned long long)P.v;
+        const unsigned long long pb = (unsigned long long)(DD ? vb : P.v);
         const unsigned phi = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb >> 32));
         const unsigned plo = (unsigned)__builtin_amdgcn_readfirstlane((int)(pb & 0xffffffffull));
-        sym_ld9(vv, reinterpret_cast<const double *>(((unsigned long long)phi << 32) | plo), o);
+        sym_ld9<NTL>(vv, reinterpret_cast<const double *>(((unsigned long long)phi << 32) | plo), o);
     };
     // 1. units from an LDS counter; each wave's first D + 2 static (w, w + WV,
     // ...: the counter starts past them -- as many as the D items issued
@@ -758,6 +766,267 @@ int brick_setup(kle_mat *A, const std::vector<int> &rb, const std::vector<int> &
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Row dedup of the value stream.  On a box mesh every element is the same
+// brick, so the assembled K repeats a few distinct rows (by the node's place
+// in its element and the Dirichlet faces its elements touch; in the compact
+// stream also by its role in a unit) over the whole lattice, once the
+// assembly makes translated rows the same bits (kle_assemble.hip
+// asm_box_uniform).  After the pack: a hash per bricked row
+// proposes groups of equal rows, a word-by-word comparison with the group's
+// first row (the smallest natural index: the same on every run) decides, and
+// the kept rows are copied into a new, smaller array; the descriptors of the
+// others point at their representative's copy.  The kernel reads the same
+// values in the same order, so the product is what the full stream gives, bit
+// for bit.
+
+__device__ __forceinline__ unsigned long long dd_mix(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// one wave per listed row: two 64-bit sums of position-keyed mixes of its
+// len[r] words from start[r] (sums: no order to fix)
+__global__ __launch_bounds__(256) void k_brick_row_hash(int64_t nr, const int64_t *__restrict__ start,
+                                                        const int *__restrict__ len, const double *__restrict__ sval,
+                                                        unsigned long long *__restrict__ h)
+{
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= nr) return;
+    const unsigned long long *v = reinterpret_cast<const unsigned long long *>(sval + start[r]);
+    unsigned long long a = 0, b = 0;
+    for (int k = lane; k < len[r]; k += 64) {
+        const unsigned long long w = v[k], p = (unsigned long long)(k + 1);
+        a += dd_mix(w ^ (p * 0x9e3779b97f4a7c15ull));
+        b += dd_mix((w + 0xd1b54a32d192ed03ull) ^ (p * 0xc2b2ae3d27d4eb4full));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if (lane == 0) {
+        h[2 * r] = a;
+        h[2 * r + 1] = b;
+    }
+}
+
+// one wave per listed row with a representative rep[r] != r: differs[r] = 1
+// unless its len[r] words equal the representative's
+__global__ __launch_bounds__(256) void k_brick_row_cmp(int64_t nr, const int64_t *__restrict__ start,
+                                                       const int *__restrict__ len, const int *__restrict__ rep,
+                                                       const double *__restrict__ sval, int *__restrict__ differs)
+{
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= nr) return;
+    const int q = rep[r];
+    if (q < 0 || q >= nr || q == r) return;
+    if (len[q] != len[r]) {
+        if (lane == 0) differs[r] = 1;
+        return;
+    }
+    const unsigned long long *v = reinterpret_cast<const unsigned long long *>(sval + start[r]);
+    const unsigned long long *u = reinterpret_cast<const unsigned long long *>(sval + start[q]);
+    bool d = false;
+    for (int k = lane; k < len[r]; k += 64) d |= v[k] != u[k];
+    if (__ballot(d) != 0ull && lane == 0) differs[r] = 1;
+}
+
+// one wave per listed row with dst[r] >= 0: its plen[r] doubles (the padding
+// with them) from src + start[r] to out + dst[r]
+__global__ __launch_bounds__(256) void k_brick_row_copy(int64_t nr, const int64_t *__restrict__ start,
+                                                        const int *__restrict__ plen, const int64_t *__restrict__ dst,
+                                                        const double *__restrict__ src, double *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= nr || dst[r] < 0) return;
+    const double *s = src + start[r];
+    double *o = out + dst[r];
+    for (int k = lane; k < plen[r]; k += 64) o[k] = s[k];
+}
+
+// The dedup (spmv_brick_dedup), after the pack and before anything else of
+// brick_finish: on success the plan's descriptors, bricks and svb, d_svptr,
+// d_sval and snvals describe the unique array; where it does not pay (fewer
+// than half of the bricked bytes saved), does not fit the descriptors' 23
+// bits or the memory is short, everything stays as it was.
+static int brick_dedup(kle_mat *A, BrickPlan &bp)
+{
+    kle_ctx *c = A->ctx;
+    const int64_t n = A->nrows, Lx = A->row_lat[0], Ly = A->row_lat[1];
+    const bool compact = !bp.rbits.empty();
+    struct Row {
+        int64_t i, rr;  // natural index, descriptor index
+        int len, plen;
+    };
+    std::vector<Row> rows;
+    for (const BrickDesc &D : bp.bricks)
+        for (int r = 0; r < D.nr; ++r) {
+            const int64_t rr = (int64_t)D.rstart + r;
+            if (brick_row_null(bp.rowd.data(), rr)) continue;
+            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
+            const int dm = compact ? 7 : 15;
+            const int dbx = dw & dm, dby = (dw >> 4) & dm, dbz = (dw >> 8) & dm;
+            const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
+            const int64_t mu = bnx * bny * bnz - (dbx + bnx * (dby + bny * dbz));
+            const int64_t len = compact ? brick_row_doubles(dw) : 9 * mu;
+            const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), rr), Lx, Ly);
+            if (i < 0 || i >= n || len < 1) return 0;  // (brick_validate names what is wrong)
+            const int64_t v0 = D.vbase + (int64_t)(bp.rowd[2 * rr + 1] & (BRICK_ROW_NULL - 1)) * 16;
+            const int64_t plen = (len + 15) & ~int64_t(15);
+            if (v0 != bp.svb[i] || v0 < 0 || v0 + plen > A->snvals) return 0;
+            rows.push_back({i, rr, (int)len, (int)plen});
+        }
+    const int64_t nr = (int64_t)rows.size();
+    if (nr < 2 || nr > INT_MAX / 2) return 0;
+    std::vector<int64_t> hstart(nr);
+    std::vector<int> hlen(nr), hplen(nr);
+    for (int64_t r = 0; r < nr; ++r) {
+        hstart[r] = bp.svb[rows[r].i];
+        hlen[r] = rows[r].len;
+        hplen[r] = rows[r].plen;
+    }
+    int64_t *dstart = nullptr, *ddst = nullptr;
+    int *dlen = nullptr, *dplen = nullptr, *drep = nullptr, *ddiff = nullptr;
+    unsigned long long *dh = nullptr;
+    struct DevFree {  // (freed on every way out)
+        void *&p;
+        ~DevFree()
+        {
+            if (p) (void)hipFree(p);
+        }
+    };
+    DevFree f0{(void *&)dstart}, f1{(void *&)ddst}, f2{(void *&)dlen}, f3{(void *&)dplen}, f4{(void *&)drep},
+        f5{(void *&)ddiff}, f6{(void *&)dh};
+    if (hipMalloc(&dstart, sizeof(int64_t) * nr) != hipSuccess || hipMalloc(&ddst, sizeof(int64_t) * nr) != hipSuccess ||
+        hipMalloc(&dlen, sizeof(int) * nr) != hipSuccess || hipMalloc(&dplen, sizeof(int) * nr) != hipSuccess ||
+        hipMalloc(&drep, sizeof(int) * nr) != hipSuccess || hipMalloc(&ddiff, sizeof(int) * nr) != hipSuccess ||
+        hipMalloc(&dh, sizeof(unsigned long long) * 2 * nr) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const dim3 grid((unsigned)((nr + 3) / 4));
+    KLE_TRY(h2d(dstart, hstart.data(), sizeof(int64_t) * nr));
+    KLE_TRY(h2d(dlen, hlen.data(), sizeof(int) * nr));
+    KLE_TRY(h2d(dplen, hplen.data(), sizeof(int) * nr));
+    // 1. hash; equal keys (length, hash) grouped on the host, the smallest
+    // natural index first.  A row's box and its role in its unit are not part
+    // of the key: each row is read through its own descriptor, only the place
+    // of its values is shared, so equal bytes are all the sharing needs (a
+    // unit's second row of the compact stream, whose last partial pass comes
+    // first, has other bytes than the same row as a first one)
+    hipLaunchKernelGGL(k_brick_row_hash, grid, dim3(256), 0, c->stream, nr, dstart, dlen, A->d_sval, dh);
+    KLE_HIP(hipGetLastError());
+    std::vector<unsigned long long> hh(2 * nr);
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    KLE_HIP(hipMemcpy(hh.data(), dh, sizeof(unsigned long long) * 2 * nr, hipMemcpyDeviceToHost));
+    std::vector<int> ord(nr), rep(nr);
+    for (int64_t r = 0; r < nr; ++r) ord[r] = (int)r;
+    auto key_less = [&](int a, int b) {
+        const Row &x = rows[a], &y = rows[b];
+        if (x.len != y.len) return x.len < y.len;
+        if (hh[2 * a] != hh[2 * b]) return hh[2 * a] < hh[2 * b];
+        if (hh[2 * a + 1] != hh[2 * b + 1]) return hh[2 * a + 1] < hh[2 * b + 1];
+        return x.i < y.i;
+    };
+    auto key_eq = [&](int a, int b) {
+        const Row &x = rows[a], &y = rows[b];
+        return x.len == y.len && hh[2 * a] == hh[2 * b] && hh[2 * a + 1] == hh[2 * b + 1];
+    };
+    std::sort(ord.begin(), ord.end(), key_less);
+    for (int64_t k = 0, g = 0; k < nr; ++k) {
+        if (!key_eq(ord[g], ord[k])) g = k;
+        rep[ord[k]] = ord[g];
+    }
+    // 2. the comparison decides: a row that differs anywhere keeps its own storage
+    KLE_TRY(h2d(drep, rep.data(), sizeof(int) * nr));
+    KLE_HIP(hipMemsetAsync(ddiff, 0, sizeof(int) * nr, c->stream));
+    hipLaunchKernelGGL(k_brick_row_cmp, grid, dim3(256), 0, c->stream, nr, dstart, dlen, drep, A->d_sval, ddiff);
+    KLE_HIP(hipGetLastError());
+    std::vector<int> diff(nr);
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    KLE_HIP(hipMemcpy(diff.data(), ddiff, sizeof(int) * nr, hipMemcpyDeviceToHost));
+    // 3. the unique array: the kept rows in brick order, each aligned to 16
+    // doubles, then the one-block rows' values (9 doubles each) as before
+    std::vector<int64_t> dst(nr, -1);
+    int64_t cur = 0, before = 0, kept = 0;
+    for (int64_t r = 0; r < nr; ++r) {
+        before += rows[r].plen;
+        if (rep[r] != r && !diff[r]) continue;
+        rep[r] = (int)r;
+        if ((cur >> 4) >= BRICK_ROW_NULL) return 0;  // (past what 23 bits x 16 doubles address: 1 GiB)
+        dst[r] = cur;
+        cur += rows[r].plen;
+        ++kept;
+    }
+    if (2 * cur > before) return 0;  // (fewer than half of the bricked bytes saved)
+    const int64_t ubytes = 8 * cur, ns = (int64_t)bp.srows.size();
+    const int64_t s_old = ns ? bp.svb[bp.srows[0]] : 0, s_new = cur;
+    for (int64_t k = 0; k < ns; ++k)
+        if (bp.svb[bp.srows[k]] != s_old + 9 * k || s_old + 9 * ns > A->snvals) return 0;
+    const int64_t total = (cur + 9 * ns + 15) & ~int64_t(15);
+    double *old = A->d_sval;
+    void *old_raw = A->sval_raw ? A->sval_raw : (void *)old;
+    const size_t old_cap = A->sval_cap;
+    if (sval_alloc(A, sizeof(double) * std::max<int64_t>(total, 1)) != 0) {
+        A->d_sval = old;
+        A->sval_raw = old_raw == (void *)old ? nullptr : old_raw;
+        A->sval_cap = old_cap;
+        return 0;
+    }
+    double *nv = A->d_sval;
+    // (until the copy is done the matrix keeps its full stream: an error
+    // return frees exactly one of the two arrays)
+    A->d_sval = old;
+    A->sval_raw = old_raw == (void *)old ? nullptr : old_raw;
+    struct NewFree {
+        double *&p;
+        ~NewFree()
+        {
+            if (p) (void)hipFree(p);
+        }
+    } fnv{nv};
+    KLE_TRY(h2d(ddst, dst.data(), sizeof(int64_t) * nr));
+    KLE_HIP(hipMemsetAsync(nv, 0, sizeof(double) * std::max<int64_t>(total, 1), c->stream));
+    hipLaunchKernelGGL(k_brick_row_copy, grid, dim3(256), 0, c->stream, nr, dstart, dplen, ddst, old, nv);
+    KLE_HIP(hipGetLastError());
+    if (ns)
+        KLE_HIP(hipMemcpyAsync(nv + s_new, old + s_old, sizeof(double) * 9 * ns, hipMemcpyDeviceToDevice, c->stream));
+    // the tables: every row's place in the unique array
+    std::vector<int64_t> svb(bp.svb);
+    for (int64_t r = 0; r < nr; ++r) svb[rows[r].i] = dst[rep[r]];
+    for (int64_t k = 0; k < ns; ++k) svb[bp.srows[k]] = s_new + 9 * k;
+    svb[n] = total;
+    KLE_TRY(h2d(A->d_svptr, svb.data(), sizeof(int64_t) * (n + 1)));
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(old_raw);
+    A->d_sval = nv;
+    nv = nullptr;
+    A->sval_raw = nullptr;
+    A->sval_cap = 0;
+    A->snvals = total;
+    bp.svb.swap(svb);
+    for (int64_t r = 0; r < nr; ++r) {
+        int &vw = bp.rowd[2 * rows[r].rr + 1];
+        vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(dst[rep[r]] >> 4);
+    }
+    for (BrickDesc &D : bp.bricks) D.vbase = 0;
+    bp.dedup = true;
+    A->brick_dedup = 1;
+    A->brick_unique_rows = kept;
+    A->brick_unique_bytes = ubytes;
+    if (const char *e = getenv("KLE_TIMING"))
+        if (atoi(e))
+            fprintf(stderr, "[kle brick r%d] dedup: %lld of %lld rows kept, %.1f of %.1f MB\n", c->rank, (long long)kept,
+                    (long long)nr, ubytes * 1e-6, 8e-6 * before);
+    return 0;
+}
+
 // after the values are in place (d_sval, d_svptr in brick layout): the brick
 // tables on the device, the workspace, the bound exponents
 int brick_finish(kle_mat *A, void *plan)
@@ -766,6 +1035,7 @@ int brick_finish(kle_mat *A, void *plan)
     kle_ctx *c = A->ctx;
     const int NB = (int)bp->bricks.size();
     const bool compact = !bp->rbits.empty();
+    if (g_tune.spmv_brick_dedup && NB > 0) KLE_TRY(brick_dedup(A, *bp));
     // every address the kernel forms from the tables, checked on the host
     // first (a bad plan is an error, never a launch)
     {
@@ -979,8 +1249,27 @@ void brick_forget(kle_mat *A)
     A->sym_brick = 0;
     A->brick_compact = 0;
     A->brick_dropped = 0;
+    A->brick_dedup = 0;
+    A->brick_unique_rows = A->brick_unique_bytes = 0;
     A->sym_gbrick = 0;
     A->brick_lds_u = 0;
+}
+
+// the brick kernel of a matrix: compact or full stream; a deduplicated value
+// array (its loads cached unless spmv_brick_dedup_nt); dot: (A x, x) shares
+using BrickKern = void (*)(int, int, int, int, int, int, const BrickDesc *, const int2 *, const double *, const double *,
+                           double *, double *, double *, const int *KLE_PROBE_PARAM);
+template <bool DOT>
+static BrickKern brick_kernel_of(const kle_mat *A)
+{
+    if (A->brick_dedup) {
+        if (g_tune.spmv_brick_dedup_nt)
+            return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true, true, true>
+                                    : k_nb_spmv_sym_brick<BRICK_WV, true, DOT, false, true, true>;
+        return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true, true, false>
+                                : k_nb_spmv_sym_brick<BRICK_WV, true, DOT, false, true, false>;
+    }
+    return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true> : k_nb_spmv_sym_brick<BRICK_WV, true, DOT>;
 }
 
 int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart, bool split)
@@ -1012,13 +1301,7 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
     } else {
         // (a split product's (A x, x): the bricks' shares, DOT; else the gather's)
         const bool dot = split && dpart && !dist;
-        if (A->brick_compact) {
-            if (dot) go(k_nb_spmv_sym_brick<BRICK_WV, true, true, true>, 0, BRICK_WV);
-            else go(k_nb_spmv_sym_brick<BRICK_WV, true, false, true>, 0, BRICK_WV);
-        } else {
-            if (dot) go(k_nb_spmv_sym_brick<BRICK_WV, true, true>, 0, BRICK_WV);
-            else go(k_nb_spmv_sym_brick<BRICK_WV, true, false>, 0, BRICK_WV);
-        }
+        go(dot ? brick_kernel_of<true>(A) : brick_kernel_of<false>(A), 0, BRICK_WV);
     }
     KLE_HIP(hipGetLastError());
     // the gather (kle_sym.hip gsym_gather): per row its direct sum in y, then
@@ -1056,8 +1339,7 @@ int brick_spmv_local(kle_mat *A, const kle_vec *x, kle_vec *y)
     const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
     const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
     if (A->nbricks > 0) {
-        auto kern = A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, false, true>
-                                     : k_nb_spmv_sym_brick<BRICK_WV, true, false>;
+        const BrickKern kern = brick_kernel_of<false>(A);
         dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * BRICK_WV), (size_t)A->brick_lds, c->stream,
                            (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp, A->brick_rstride,

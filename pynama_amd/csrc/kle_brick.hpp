@@ -106,6 +106,10 @@ struct BrickPlan {
     // its stream -- and the entries the stream leaves out
     std::vector<unsigned char> rbits, second;
     int64_t dropped = 0;
+    // deduplicated values (kle_brick.hip brick_dedup): rows with bitwise equal
+    // streams share one copy, every brick's vbase is 0, and a unit's second
+    // row may lie anywhere in the value array
+    bool dedup = false;
 };
 // a row's descriptor word 0 with its boundary bits (compact stream)
 KLE_BRICK_HD inline int brick_dw_bits(int srow, int rb)

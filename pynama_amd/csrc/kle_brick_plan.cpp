@@ -601,7 +601,9 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
 // block k0 < its box's size (mu >= 1 stored blocks), region index inside the
 // brick's region and its lattice node inside the owned lattice, its values
 // [off 16, off 16 + 9 mu) (the compact stream: + brick_row_doubles) inside the value array, a unit's second row's
-// values after its first's; regions within the LDS.  nullptr: consistent.
+// values after its first's (deduplicated values: anywhere in the array, every
+// brick's vbase 0); regions within the LDS and their sums within the
+// workspace.  nullptr: consistent.
 const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t Lz, int64_t nvals,
                                   int64_t lds_cap)
 {
@@ -611,6 +613,7 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
         if ((int64_t)brick_lds((int)RN) > std::min<int64_t>(lds_cap, (int64_t)BRICK_LDS_CAP))
             return "a brick's region exceeds the LDS";
         if (D.rstart < 0 || 2 * ((int64_t)D.rstart + D.nr) > (int64_t)bp.rowd.size()) return "a brick's rows";
+        if (D.wsoff < 0 || D.wsoff + 3 * RN > bp.ws_doubles) return "a brick's region sums";
         int64_t a_v0 = 0;
         for (int r = 0; r < D.nr; ++r) {
             const int64_t rr = (int64_t)D.rstart + r;
@@ -634,7 +637,11 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
             const int64_t v1 = v0 + (compact ? brick_row_doubles(dw & 0xFFFFFF) : 9 * (int64_t)mu);
             if (v0 < 0 || v1 > nvals) return "a row's values";
             if (r % 2 == 0) a_v0 = v0;
-            else if (v0 < a_v0 || v0 - a_v0 > ((int64_t)1 << 26)) return "a unit's second row's values";
+            else if (!bp.dedup && (v0 < a_v0 || v0 - a_v0 > ((int64_t)1 << 26))) return "a unit's second row's values";
+            // (deduplicated: the kernel's 32-bit byte offsets start at the array, not at the unit's first
+            // row; with every vbase 0 the descriptor's 23 bits keep a row's end below 2^27 + 2^15 doubles,
+            // so the byte offset between any two rows fits)
+            if (bp.dedup && D.vbase != 0) return "a deduplicated row's values";
         }
     }
     return nullptr;
@@ -642,23 +649,15 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
 
 }  // namespace kle
 
-// Diagnostic (host only, no device): the brick plan of an Lx x Ly x Lz box
-// lattice of p-node elements (element-aligned row boxes, the pattern of
-// MatFS.buildFS on a box mesh, mat_fs.py:21-94) for ncu CUs -- what the
-// symmetric storage of such a K would run (kle_sym.hip, one rank).
-// dirichlet: every boundary node is a Dirichlet node -- its row the diagonal
-// block alone, its column in no other row (the K of buildFS with Dirichlet
-// data on all faces, as the bench's Taylor-Green case).
-// info[0] bricks, [1] bricks along x, [2] y, [3] z, [4] LDS bytes;
-// stats[0] bytes of the largest brick / the mean, [1] region entries per row,
-// [2] stored blocks, [3] the planner's time model (us).  Returns KLE_ERR_SUP (with the reason) when no plan fits.
-extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int rounds, int split,
-                                  int *info, double *stats)
+// the node-block pattern of MatFS.buildFS on an Lx x Ly x Lz box lattice of
+// p-node elements (element-aligned row boxes; dirichlet: every boundary node
+// a Dirichlet node): per row its block count and packed box; returns the
+// stored upper blocks
+static int64_t box_pattern(int Lx, int Ly, int Lz, int p, int dirichlet, std::vector<int> &cnt, std::vector<int> &srow)
 {
-    using namespace kle;
-    KLE_ARG(Lx >= 1 && Ly >= 1 && Lz >= 1 && p >= 1 && p <= 7 && ncu >= 1 && info && stats, "bad arg");
     const int64_t n = (int64_t)Lx * Ly * Lz;
-    std::vector<int> cnt(n), srow(n);
+    cnt.assign(n, 0);
+    srow.assign(n, 0);
     auto box = [&](int c, int L, int &b, int &nb) {  // element-aligned box of coordinate c
         const int e = c / p;
         const bool onb = c % p == 0;
@@ -688,6 +687,27 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
                 srow[i] = (x - bx) | (y - by) << 4 | (z - bz) << 8 | nx << 12 | ny << 16 | nz << 20;
                 blocks += cnt[i] - ((x - bx) + nx * ((y - by) + ny * (z - bz)));
             }
+    return blocks;
+}
+
+// Diagnostic (host only, no device): the brick plan of an Lx x Ly x Lz box
+// lattice of p-node elements (element-aligned row boxes, the pattern of
+// MatFS.buildFS on a box mesh, mat_fs.py:21-94) for ncu CUs -- what the
+// symmetric storage of such a K would run (kle_sym.hip, one rank).
+// dirichlet: every boundary node is a Dirichlet node -- its row the diagonal
+// block alone, its column in no other row (the K of buildFS with Dirichlet
+// data on all faces, as the bench's Taylor-Green case).
+// info[0] bricks, [1] bricks along x, [2] y, [3] z, [4] LDS bytes;
+// stats[0] bytes of the largest brick / the mean, [1] region entries per row,
+// [2] stored blocks, [3] the planner's time model (us).  Returns KLE_ERR_SUP (with the reason) when no plan fits.
+extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int rounds, int split,
+                                  int *info, double *stats)
+{
+    using namespace kle;
+    KLE_ARG(Lx >= 1 && Ly >= 1 && Lz >= 1 && p >= 1 && p <= 7 && ncu >= 1 && info && stats, "bad arg");
+    const int64_t n = (int64_t)Lx * Ly * Lz;
+    std::vector<int> cnt, srow;
+    const int64_t blocks = box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
     BrickPlan bp;
     bp.singles = g_tune.spmv_brick_singles;
     bp.pair = g_tune.spmv_brick_pair;
@@ -803,5 +823,76 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
             fprintf(stderr, "brick %d %d %d  %d %d %d  rows %d  region %d %d %d  w %.4f  blocks %lld  one %d  multi %d\n",
                     D.x0, D.y0, D.z0, D.nx, D.ny, D.nz, D.nr, D.RX, D.RY, D.RZ, weight(D) / (tot / NB), sb, one, two);
         }
+    return 0;
+}
+
+// Diagnostic (host only): the plan of kle_brick_plan_box with its value
+// offsets rewritten as the row dedup (kle_brick.hip brick_dedup) rewrites
+// them for a K whose rows with equal packed boxes are equal -- the first such
+// row in brick order keeps its values, the others point at them, every
+// brick's vbase is 0 -- and checked by brick_validate against the unique
+// array.  shift > 0 first moves the last row's offset that many 16-double
+// units on: past the array, which the validator must refuse (KLE_ERR_SUP).
+// shift -1 instead gives the last brick a base of its own, 16 doubles, inside
+// an array that many doubles longer: every range still inside, refused for
+// the base.
+// out[0] rows in bricks, out[1] rows stored, out[2] doubles of the unique array.
+extern "C" int kle_brick_plan_box_shared(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int shift,
+                                         long long *out)
+{
+    using namespace kle;
+    KLE_ARG(Lx >= 1 && Ly >= 1 && Lz >= 1 && p >= 1 && p <= 7 && ncu >= 1 && shift >= -1 && out, "bad arg");
+    const int64_t n = (int64_t)Lx * Ly * Lz;
+    std::vector<int> cnt, srow;
+    (void)box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
+    BrickPlan bp;
+    bp.singles = g_tune.spmv_brick_singles;
+    bp.pair = g_tune.spmv_brick_pair;
+    const std::string why = brick_plan(Lx, Ly, Lz, 0, ncu, 0, 1, 0, cnt, srow, p, bp);
+    if (!why.empty()) return fail(KLE_ERR_SUP, "%s", why.c_str());
+    if (const char *bad = brick_validate(bp, Lx, Ly, Lz, bp.svb[n], (int64_t)bp.lds))
+        return fail(KLE_ERR_SUP, "brick plan: %s", bad);
+    std::vector<std::pair<int, int64_t>> first;  // (packed box, offset of the row that keeps its values)
+    int64_t cur = 0, rows = 0, kept = 0, last = -1;
+    for (BrickDesc &D : bp.bricks) {
+        for (int r = 0; r < D.nr; ++r) {
+            const int64_t rr = (int64_t)D.rstart + r;
+            if (brick_row_null(bp.rowd.data(), rr)) continue;
+            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
+            const int k0 = (dw & 15) + ((dw >> 12) & 15) * (((dw >> 4) & 15) + ((dw >> 16) & 15) * ((dw >> 8) & 15));
+            const int64_t mu = ((dw >> 12) & 15) * ((dw >> 16) & 15) * ((dw >> 20) & 15) - k0;
+            int64_t off = -1;
+            for (const auto &f : first)
+                if (f.first == dw) off = f.second;
+            if (off < 0) {
+                off = cur;
+                first.push_back({dw, off});
+                cur += (9 * mu + 15) & ~int64_t(15);
+                ++kept;
+            }
+            int &vw = bp.rowd[2 * rr + 1];
+            vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(off >> 4);
+            last = rr;
+            ++rows;
+        }
+        D.vbase = 0;
+    }
+    bp.dedup = true;
+    int64_t total = (cur + 9 * (int64_t)bp.srows.size() + 15) & ~int64_t(15);
+    if (shift < 0 && !bp.bricks.empty()) {
+        bp.bricks.back().vbase = 16;
+        total += 16;
+    }
+    if (shift > 0 && last >= 0) {
+        int &vw = bp.rowd[2 * last + 1];
+        const int64_t o = (int64_t)(vw & (BRICK_ROW_NULL - 1)) + shift;
+        KLE_ARG(o < BRICK_ROW_NULL, "shift beyond the descriptor's 23 bits");
+        vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)o;
+    }
+    out[0] = rows;
+    out[1] = kept;
+    out[2] = total;
+    if (const char *bad = brick_validate(bp, Lx, Ly, Lz, total, (int64_t)bp.lds))
+        return fail(KLE_ERR_SUP, "brick plan: %s", bad);
     return 0;
 }

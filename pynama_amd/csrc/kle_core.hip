@@ -883,6 +883,18 @@ int kle_set_tuning(const char *key, int value)
     } else if (k == "spmv_brick_compact") {
         KLE_ARG(value == 0 || value == 1, "spmv_brick_compact: 0 or 1");
         g_tune.spmv_brick_compact = value;
+    } else if (k == "spmv_brick_dedup") {
+        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup: 0 or 1");
+        g_tune.spmv_brick_dedup = value;
+    } else if (k == "spmv_brick_dedup_full") {
+        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup_full: 0 or 1");
+        g_tune.spmv_brick_dedup_full = value;
+    } else if (k == "spmv_brick_dedup_nt") {
+        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup_nt: 0 or 1");
+        g_tune.spmv_brick_dedup_nt = value;
+    } else if (k == "asm_box_uniform") {
+        KLE_ARG(value == 0 || value == 1, "asm_box_uniform: 0 or 1");
+        g_tune.asm_box_uniform = value;
     } else if (k == "asm_box_zeros") {
         KLE_ARG(value == 0 || value == 1, "asm_box_zeros: 0 or 1");
         g_tune.asm_box_zeros = value;
@@ -939,7 +951,11 @@ int kle_get_tuning(const char *key, int *value)
     else if (k == "spmv_brick_pair") *value = g_tune.spmv_brick_pair;
     else if (k == "elem_ghost_rows") *value = g_tune.elem_ghost_rows;
     else if (k == "asm_box_zeros") *value = g_tune.asm_box_zeros;
+    else if (k == "asm_box_uniform") *value = g_tune.asm_box_uniform;
     else if (k == "spmv_brick_compact") *value = g_tune.spmv_brick_compact;
+    else if (k == "spmv_brick_dedup") *value = g_tune.spmv_brick_dedup;
+    else if (k == "spmv_brick_dedup_nt") *value = g_tune.spmv_brick_dedup_nt;
+    else if (k == "spmv_brick_dedup_full") *value = g_tune.spmv_brick_dedup_full;
     else if (k == "spmv_gather_wps") *value = g_tune.spmv_gather_wps;
     else if (k == "spmv_gsym_brick") *value = g_tune.spmv_gsym_brick;
     else if (k == "upd_unroll") *value = g_tune.upd_unroll;

@@ -288,6 +288,8 @@ struct kle_mat {
     double brick_model_us = 0.0;    // the planner's modelled product time
     int brick_compact = 0;          // the bricks' value stream leaves out the analytic zeros (kle_brick.hpp)
     int64_t brick_dropped = 0;      // ... this many entries
+    int brick_dedup = 0;            // the bricks' rows with bitwise equal streams share one copy (kle_brick.hip brick_dedup)
+    int64_t brick_unique_rows = 0, brick_unique_bytes = 0;  // ... the stored rows and their bytes
     void *d_bdesc = nullptr;
     int *d_browd = nullptr;
     int64_t *d_sbp = nullptr;     // per row: its first stored block in d_slid
@@ -513,10 +515,14 @@ struct Tuning {
     int spmv_gsym_brick = 1;   // unstructured symmetric SpMV (read at build): row bricks (kle_gbrick.hip), 0 the 64-row groups
     int spmv_gather_wps = 0;   // run-mask gather: waves per 64-row slice (1, 2, 4; 0 auto by the runs per slice)
     int spmv_brick_compact = 1;  // brick SpMV (read at build): a K whose analytic zeros (kle_assemble.hip box_zero_entry) are all stored as exact zeros streams the other entries alone; 0 the full 9-entry blocks
+    int spmv_brick_dedup = 1;  // brick SpMV (read at build): bricked rows whose value streams are bitwise equal are stored once (checked by comparison; kept only where it saves half the bytes); 0 every row's own stream
+    int spmv_brick_dedup_full = 1;  // brick SpMV (read at build): a K whose rows are shared keeps the full 9-entry blocks (built first; the compact stream where the sharing is not taken); 0 the compact stream first, shared or not
+    int spmv_brick_dedup_nt = 0;  // brick SpMV (read per product): value loads of a deduplicated K 1 nontemporal as the full stream's, 0 plain cached
     int spmv_brick_pair = 1;  // brick SpMV (read at build): rows in units of two whose tails share one 64-lane item
     int spmv_brick_singles = 1;  // brick SpMV (read at build): rows of one stored block formed by the gather, not as 64-lane items of the bricks
     int spmv_brick_split = 0;  // brick SpMV (read at build): force nbx + 100 nby + 10000 nbz bricks (0: planned)
     int elem_ghost_rows = 1;  // element-wise K / Krhs / Rw on N > 1: a ghost-layer element's GEMM covers the 128-row groups holding its top-plane rows alone (1); 0 every group (same bits: the other rows are never gathered)
+    int asm_box_uniform = 1;  // assembly of a box mesh's free-slip K, Krhs and Rw (read at assembly): every cell adds the blocks of global element 0's matrices, so translated rows are the same bits (the brick SpMV then stores them once); 0 each cell's own matrix, whose coordinate rounding differs
     int asm_box_zeros = 1;  // assembly of a 3-D box mesh's free-slip K (read at assembly): the analytically zero block entries (kle_assemble.hip box_zero_entry) stored as +0.0; 0 their rounding noise (A/B and diagnosis)
     int spmv_sym_brick = 1;   // box symmetric storage, one rank (read at build): one brick per CU, sums in LDS for the whole stream (kle_brick.hip); 0 the 128-row tiles
 #ifdef KLE_PROBE_BUILD

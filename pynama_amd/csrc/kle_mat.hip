@@ -1594,6 +1594,16 @@ int kle_mat_get_brick_compact(const kle_mat *A, int *compact, long long *dropped
     return 0;
 }
 
+int kle_mat_get_brick_dedup(const kle_mat *A, int *dedup, long long *unique_rows, long long *unique_bytes)
+{
+    KLE_ARG(A && dedup && unique_rows && unique_bytes, "null arg");
+    const bool on = A->d_sval && A->sym_brick && A->brick_dedup;
+    *dedup = on;
+    *unique_rows = on ? (long long)A->brick_unique_rows : 0;
+    *unique_bytes = on ? (long long)A->brick_unique_bytes : 0;
+    return 0;
+}
+
 int kle_mat_set_symmetric(kle_mat *A, int on)
 {
     KLE_ARG(A, "null matrix");

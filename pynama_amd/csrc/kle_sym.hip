@@ -2016,7 +2016,7 @@ static int sym_probe(kle_mat *A, double vmax_all, bool &bad)
 // largest entry or whose pattern is not symmetric.  At N > 1 collective: every
 // rank decides the same way (any_rank), so no rank runs the symmetric SpMV
 // and its reverse halo while a neighbour runs the full storage.
-static int sym_build_impl(kle_mat *A);
+static int sym_build_impl(kle_mat *A, bool full_first);
 // a device scratch buffer freed when its scope ends
 struct DevFree {
     void *&p;
@@ -2029,14 +2029,39 @@ struct DevFree {
 // Every error return of the builders, wherever it happens (a refused check,
 // a device error between the allocations and the last check), leaves A
 // without symmetric storage: no SpMV can run over a half-built copy.
+// spmv_brick_dedup_full: a deduplicated value array is read from the caches,
+// and the brick kernel is then bound by its own instructions, of which the
+// compact stream's per-lane offsets (ballots, counts, nine selects per item)
+// are a good part: the full 9-entry blocks multiply faster there (config 2:
+// 260 us against 322 us; 415 against 372 us without the sharing).  So a box K
+// is first built in the full layout; where its rows are then shared it stays
+// so, and where they are not (on any rank) it is rebuilt as before, compact
+// where K allows it.
 int sym_build(kle_mat *A)
 {
-    const int rc = sym_build_impl(A);
+    int rc = 0;
+    const bool box = A->kind == 0 && A->d_rowbox;
+    if (box && g_tune.spmv_sym_brick && g_tune.spmv_brick_dedup && g_tune.spmv_brick_dedup_full &&
+        g_tune.spmv_brick_compact) {
+        rc = sym_build_impl(A, true);
+        // (both flags from every rank, whatever this one's rc: a rank that
+        // failed alone must not leave its peers waiting in the collective)
+        bool any_fail = false, again = false;
+        int arc = any_rank(A->ctx, rc != 0, any_fail);
+        if (!arc) arc = any_rank(A->ctx, !rc && A->sym_brick && !A->brick_dedup, again);
+        if (!rc && arc) rc = arc;
+        if (!rc && any_fail) rc = fail(KLE_ERR_SUP, "symmetric storage failed on another rank");
+        if (rc) sym_drop(A);
+        if (rc || !again) return rc;
+    }
+    rc = sym_build_impl(A, false);
     if (rc) sym_drop(A);
     return rc;
 }
 
-static int sym_build_impl(kle_mat *A)
+// full_first: the first pass of sym_build above -- the bricks take the full
+// 9-entry blocks whatever spmv_brick_compact says
+static int sym_build_impl(kle_mat *A, bool full_first)
 {
     kle_ctx *c = A->ctx;
     sym_drop(A);
@@ -2142,7 +2167,7 @@ static int sym_build_impl(kle_mat *A)
         // the compact value stream: only where every entry it would leave out
         // is stored as +0.0 (the check decides, on every rank alike)
         std::vector<unsigned char> rbits;
-        if (g_tune.spmv_brick_compact) {
+        if (g_tune.spmv_brick_compact && !full_first) {
             unsigned long long *dc = nullptr, hc = 1;
             unsigned char *db = nullptr;
             DevFree fdc{(void *&)dc}, fdb{(void *&)db};  // (freed on every way out)

@@ -80,24 +80,46 @@ __device__ __forceinline__ double fx_to_d(unsigned long long u)
 // front of them at every second item.  The wait for an item (vmcnt(9): the
 // next item's 9 loads stay in flight) names its 9 registers as read-write
 // operands, so nothing reads them before the data has landed.
+// (NT false: plain cached loads -- a deduplicated brick stream, kle_brick.hip,
+// is re-read by every brick and lives in the caches)
+template <bool NT = true>
 __device__ __forceinline__ void sym_ld9(double *v, const double *base, const unsigned *o)
 {
-    asm volatile(
-        "s_nop 4\n\t"
-        "global_load_dwordx2 %0, %9, %18 nt\n\t"
-        "global_load_dwordx2 %1, %10, %18 nt\n\t"
-        "global_load_dwordx2 %2, %11, %18 nt\n\t"
-        "global_load_dwordx2 %3, %12, %18 nt\n\t"
-        "global_load_dwordx2 %4, %13, %18 nt\n\t"
-        "global_load_dwordx2 %5, %14, %18 nt\n\t"
-        "global_load_dwordx2 %6, %15, %18 nt\n\t"
-        "global_load_dwordx2 %7, %16, %18 nt\n\t"
-        "global_load_dwordx2 %8, %17, %18 nt"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]),
-          "=&v"(v[8])
-        : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "v"(o[8]),
-          "s"(base)
-        : "memory");
+    if constexpr (NT) {
+        asm volatile(
+            "s_nop 4\n\t"
+            "global_load_dwordx2 %0, %9, %18 nt\n\t"
+            "global_load_dwordx2 %1, %10, %18 nt\n\t"
+            "global_load_dwordx2 %2, %11, %18 nt\n\t"
+            "global_load_dwordx2 %3, %12, %18 nt\n\t"
+            "global_load_dwordx2 %4, %13, %18 nt\n\t"
+            "global_load_dwordx2 %5, %14, %18 nt\n\t"
+            "global_load_dwordx2 %6, %15, %18 nt\n\t"
+            "global_load_dwordx2 %7, %16, %18 nt\n\t"
+            "global_load_dwordx2 %8, %17, %18 nt"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]),
+              "=&v"(v[8])
+            : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "v"(o[8]),
+              "s"(base)
+            : "memory");
+    } else {
+        asm volatile(
+            "s_nop 4\n\t"
+            "global_load_dwordx2 %0, %9, %18\n\t"
+            "global_load_dwordx2 %1, %10, %18\n\t"
+            "global_load_dwordx2 %2, %11, %18\n\t"
+            "global_load_dwordx2 %3, %12, %18\n\t"
+            "global_load_dwordx2 %4, %13, %18\n\t"
+            "global_load_dwordx2 %5, %14, %18\n\t"
+            "global_load_dwordx2 %6, %15, %18\n\t"
+            "global_load_dwordx2 %7, %16, %18\n\t"
+            "global_load_dwordx2 %8, %17, %18"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]),
+              "=&v"(v[8])
+            : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "v"(o[8]),
+              "s"(base)
+            : "memory");
+    }
 }
 
 template <int N>

@@ -556,8 +556,11 @@ class Mat:
             return None
         cp, dr = C.c_int(), C.c_longlong()
         call("kle_mat_get_brick_compact", self._h, C.byref(cp), C.byref(dr))
+        dd, ur, ub = C.c_int(), C.c_longlong(), C.c_longlong()
+        call("kle_mat_get_brick_dedup", self._h, C.byref(dd), C.byref(ur), C.byref(ub))
         return {"bricks": n.value, "dims": list(dims), "region_entries_per_row": ent.value, "model_us": mus.value,
-                "compact": bool(cp.value), "dropped_entries": dr.value}
+                "compact": bool(cp.value), "dropped_entries": dr.value,
+                "dedup": bool(dd.value), "unique_rows": ur.value, "unique_bytes": ub.value}
 
     def moveValues(self, shift, fresh=True):
         """Diagnostic: the symmetric storage's values `shift` bytes into a

@@ -29,10 +29,13 @@ def median(d, name):
     want = name.replace(" ", "") + "("  # (rocprofv3 names carry "void kle::" and the argument list)
     # (the brick kernel on the compact value stream is the same reported
     # kernel with one more template argument, kle_brick.hip CP)
+    # (... and with further ones on a deduplicated value array, kle_brick.hip
+    # DD and NTL: any instantiation whose arguments start with the reported ones)
     alt = want[:-2] + ",true>(" if want.startswith("k_nb_spmv_sym_brick<") else want
+    more = want[:-2] + "," if want.startswith("k_nb_spmv_sym_brick<") else want
     v = [float(r["Counter_Value"]) for r in csv.DictReader(open(f))
          if any(w in r["Kernel_Name"].replace(" ", "").replace("voidkle::", "").replace("kle::", "")
-                for w in (want, alt))]
+                for w in (want, alt, more))]
     if not v:
         raise SystemExit(f"pmc_traffic: no dispatch of {name} in {f}")
     v.sort()
