@@ -69,100 +69,124 @@ typedef struct kle_mat kle_mat;
 typedef struct kle_ksp kle_ksp;
 
 const char *kle_last_error(void);
-/* Performance knobs for in-process A/B measurements (tools/cg_ab.py); every
- * value gives bitwise the same results, except the symmetric-storage keys
- * (the same product to rounding).  Keys: "spmv_waves" (0 auto, 4, 8:
- * rows per SpMV workgroup of 3x3 chunked matrices), "spmv_x_lds" (1 default:
- * structured 3x3 rows at 8 waves stage x in LDS; 0 off), "spmv_xcd_chunk"
- * (row blocks per XCD run, 0 round-robin; default 16), "spmv_dyn_lds" (unused
- * LDS bytes per SpMV workgroup while side-stream work runs, -1 auto),
- * "spmv_dict" (1 default: unstructured 3x3 rows at 8 waves read x through
- * per-group column dictionaries; 0 off), "spmv_dict_min_rows" (node rows from
- * which matrices get dictionaries at creation; default 64000), "upd_preload"
- * (1 default: CG update kernels load their first element and the stage inputs
- * before the prologue; 0 off), "upd_nt" (single-reduction CG update: every
- * vector but u loaded and stored nontemporal, so u stays in the Infinity
- * Cache for the SpMV; 0 off, 1 on, 2 auto = from 2M local entries), "spmv_sym" (1 default: matrices holding
- * symmetric storage run the symmetric SpMV; 0 the full storage),
- * "spmv_sym_min_rows" (node rows per rank from which kle_assemble_kle gives
- * K symmetric storage; default 40000), "spmv_sym_tz" (read when the storage
- * is built: 0 auto = 8 x 4 x 4-row tiles where two 8-wave workgroups fit a
- * CU, 2 = 8 x 8 x 2, 4 = 8 x 4 x 4), "spmv_sym_det" (1
- * default: the transposed adds as exact fixed-point sums, y bitwise
- * reproducible; 0 fp64 LDS atomics, reproducible to rounding),
- * "ksp_refine" (correction solves of new KSPs, kle_ksp_set_corrections:
- * default 2, 0 PETSc's plain stop -- KLE_KSP_REFINE),
- * "spmv_sym_waves" (0 auto, 8 or 16 waves per workgroup), "spmv_gsym_rows"
- * (read when the storage of an
- * unstructured K is built: rows per group, 64 default, 128, 32, 16 or 8),
- * "spmv_gsym_waves" (read at build: 0 auto = 16 for 64-row groups, else 8;
- * 8 or 16), "spmv_gsym_split" (read at build: the largest dictionary of the
- * first of its two launches; 0 auto), "spmv_sym_brick" (read at build:
- * the box K of one rank on bricks -- one 16-wave workgroup per CU, the
- * brick region's x and exact sums in LDS for the whole value stream; 1
- * default, 0 the 128-row tiles), "spmv_brick_max" (read at
- * build: at most this many bricks, 0 planned), "spmv_brick_rounds" (read at
- * build: at most this many bricks per CU, default 1), "spmv_brick_split" (read
- * at build: force nbx + 100 nby + 10000 nbz bricks, 0 planned),
- * "spmv_brick_pair" (read at build: rows in units of two whose last
- * partial 64-block passes share one item; 1 default), "spmv_brick_singles"
- * (read at build: rows of one stored block -- the Dirichlet rows and the
- * free rows at the far corner of their box -- formed by the gather instead
- * of as items of the bricks; 1 default), "spmv_brick_dedup" (read at build:
- * bricked rows whose value streams are bitwise equal -- a box-mesh K repeats
- * a few distinct rows over the lattice -- are stored once; proposed by a
- * hash, decided by comparison, kept only where it saves at least half of the
- * bricked bytes and fits the descriptors' 1 GiB; the product is bitwise the
- * same; 1 default, 0 every row's own stream), "spmv_brick_dedup_nt" (value
- * loads of a deduplicated K: 0 default plain cached, 1 nontemporal as the
- * full stream's), "spmv_brick_dedup_full" (read at build: a K whose rows are
- * shared keeps the full 9-entry blocks -- read from the caches, the kernel is
- * bound by its instructions and the compact stream's offsets cost more than
- * its bytes save; the full layout is built first and the compact one only
- * where the sharing is not taken; 1 default, 0 the compact stream first),
- * "asm_box_uniform" (read at assembly: on a box mesh every cell adds the
- * blocks of global element 0's K_e and Rw_e into the free-slip K, Krhs and
- * Rw, so rows that are translates of each other are the same bits and the
- * brick SpMV stores them once; the values move by coordinate rounding,
- * <= 1e-12 of the largest entry; 1 default, 0 each cell's own matrix),
- * "spmv_gather_wps" (the run-mask
- * gather's waves per 64-row slice: 1, 2, 4; 0 default, by the runs per
- * slice), "elem_ghost_rows" (element-wise K, Krhs, Rw on several ranks: the
- * ghost layer's GEMM over the row groups holding its top-plane rows alone;
- * 1 default, 0 every row group), "spmv_gsym_brick" (read at build: graph K on graph bricks, whole
- * rounds per CU; 1 default), "ipc_sentinel" (IPC transport debug mode:
- * consumed mailbox slots overwritten with NaN before the ack; 0 default),
- * "ksp_corr_fault" (test hook: correction solves that end in NaN; 0),
- * "upd_unroll" (CG update kernel: 1 default or 2), "ksp_pipe_gather" (box
- * bricks: the pipelined CG's update gathers the split product itself; 1
- * default, 0 a separate gather launch), "ksp_sr_gather" (the same for the
- * single-reduction CG at one rank, the bricks forming (A u, u): 1 default
- * from 2^17 node rows, 2 always, 0 never),
- * "spmv_sym_tile64" (read at build: 8 x 2 x 4-row tiles -- 0 auto, below
- * "spmv_sym_tile64_max" (640) 128-row tiles; 1 wherever two workgroups fit
- * a CU; 2 never), "spmv_sym_ovl_b" (N > 1, box symmetric SpMV with halo
- * overlap: the percentage of the interior tiles run beside the reverse halo,
- * the rest beside the forward halo; default 50), "spmv_sym_early" (box tile kernel loads its first items before
- * x is in LDS; 0 default), "spmv_sym_align" (read at build: partial slots
- * aligned to 128-B lines; 0 default), "spmv_sym_stpol"
- * (box kernel's partial stores: 0 plain default, 1 nontemporal, 2 sc1, 3 sc0
- * sc1), "spmv_gsym_stpol" (the same for the graph kernel; default 2),
- * "spmv_brick_compact" (read at build: the brick value stream of a K that
- * stores every analytically zero entry as +0.0 -- checked on the device when
- * the storage is built -- holds the other entries alone, 3, 5 or 9 per block;
- * 1 default, 0 the full blocks.  The product is the same matrix's either
- * way: the entries left out are exact zeros),
- * "asm_box_zeros" (read at assembly; an A/B and diagnosis switch, not a
- * performance knob: the free-slip K of a 3-D kle_mesh_create_box mesh stores
- * its analytically zero block entries as +0.0 -- entry (a, b), a != b, of the
- * block between two nodes that share lattice coordinate a or b on a plane
- * that is not a domain boundary plane; 1 default, 0 the assembly's rounding
- * noise there, a few 1e-16 of max|K|.  Every other entry, the pattern, Krhs,
- * Rw, the operators, the no-slip matrices, 2-D and unstructured meshes are
- * the same bits for both values).
- * Every value gives correct results (the
- * timing probes of the symmetric SpMV exist only in the tools/ probe build,
- * `make -C pynama_amd/csrc probe`). */
+/* Tuning keys (kle_set_tuning, kle_get_tuning), for in-process A/B
+ * measurements (tools/cg_ab.py).  One entry per key: its values with the
+ * default marked *, then when the library reads it -- [call] at every product
+ * or solve, [build] when a matrix's SpMV storage is built, [assembly] by
+ * kle_assemble_kle and its kin, [create] when a matrix or KSP is created.
+ * Except where an entry says otherwise every value gives bitwise the same
+ * results; the symmetric-storage keys give the same product to rounding.
+ *
+ * 3x3 SpMV (full storage)
+ *   "spmv_waves"          0* auto (8 from 64000 node rows, else 4), 4, 8 [call]: rows per SpMV workgroup of
+ *                         3x3 chunked matrices
+ *   "spmv_x_lds"          0, 1* [call]: structured 3x3 rows at 8 waves stage x in LDS
+ *   "spmv_xcd_chunk"      0 .. 4096, 16* [call]: consecutive row blocks per XCD run; 0 round-robin
+ *   "spmv_dyn_lds"        -1* auto, 0 .. 65536 [call]: unused LDS bytes per SpMV workgroup while side-stream
+ *                         work runs (caps the workgroups per CU)
+ *   "spmv_dict"           0, 1* [call]: unstructured 3x3 rows at 8 waves read x through per-group column
+ *                         dictionaries
+ *   "spmv_dict_min_rows"  >= 0, 64000* [create]: node rows from which matrices get dictionaries
+ *
+ * Symmetric storage and its 128-row tiles
+ *   "spmv_sym"            0, 1* [call, assembly]: matrices holding symmetric storage run the symmetric
+ *                         SpMV, and kle_assemble_kle builds that storage; 0 the full storage
+ *   "spmv_sym_min_rows"   >= 0, 40000* [assembly]: node rows per rank from which kle_assemble_kle gives K
+ *                         symmetric storage
+ *   "spmv_sym_det"        0, 1* [call, build]: the transposed adds as exact fixed-point sums, y bitwise
+ *                         reproducible; 0 fp64 LDS atomics, reproducible to rounding (and no bricks)
+ *   "spmv_sym_waves"      0* auto, 8, 16 [call]: waves per workgroup of the box tile kernel
+ *   "spmv_sym_tz"         0* auto (8 x 4 x 4-row tiles where two 8-wave workgroups fit a CU), 2 (8 x 8 x 2),
+ *                         4 (8 x 4 x 4) [build]
+ *   "spmv_sym_tile64"     0* auto, 1, 2 [build]: 8 x 2 x 4-row tiles (64 rows) -- 0 below
+ *                         "spmv_sym_tile64_max" 128-row tiles, 1 wherever two workgroups fit a CU, 2 never
+ *   "spmv_sym_tile64_max" >= 0, 640* [build]: the 128-row tile count below which "spmv_sym_tile64" 0
+ *                         takes the 64-row tiles
+ *   "spmv_sym_xcd"        0* .. 4096 [call]: the box tile kernel's runs of this many consecutive tiles per
+ *                         XCD; 0 round-robin
+ *   "spmv_sym_ovl_b"      0 .. 100, 50* [call]: N > 1, box symmetric SpMV with halo overlap: the percentage
+ *                         of the interior tiles run beside the reverse halo, the rest beside the forward halo
+ *   "spmv_sym_early"      0*, 1 [call]: the box tile kernel loads its first items before x is in LDS
+ *   "spmv_sym_align"      0*, 1 [build]: partial slots aligned to 128-B lines
+ *   "spmv_sym_stpol"      0* plain, 1 nontemporal, 2 sc1, 3 sc0 sc1 [call]: the box kernel's partial stores
+ *
+ * Box bricks (the box K of one rank)
+ *   "spmv_sym_brick"      0, 1* [build]: the box K on bricks -- one 16-wave workgroup per CU, the brick
+ *                         region's x and exact sums in LDS for the whole value stream; 0 the 128-row tiles
+ *   "spmv_brick_max"      >= 0, 0* planned [build]: at most this many bricks
+ *   "spmv_brick_rounds"   1* .. 4 [build]: at most this many bricks per CU
+ *   "spmv_brick_split"    >= 0, 0* planned [build]: force nbx + 100 nby + 10000 nbz bricks
+ *   "spmv_brick_pair"     0, 1* [build]: rows in units of two whose last partial 64-block passes share one
+ *                         item
+ *   "spmv_brick_singles"  0, 1* [build]: rows of one stored block -- the Dirichlet rows and the free rows at
+ *                         the far corner of their box -- formed by the gather instead of as items of the
+ *                         bricks
+ *   "spmv_brick_compact"  0, 1* [build]: the brick value stream of a K that stores every analytically zero
+ *                         entry as +0.0 -- checked on the device when the storage is built -- holds the
+ *                         other entries alone, 3, 5 or 9 per block; 0 the full blocks.  The product is the
+ *                         same matrix's either way: the entries left out are exact zeros
+ *   "spmv_brick_dedup"    0, 1* [build]: bricked rows whose value streams are bitwise equal -- a box-mesh K
+ *                         repeats a few distinct rows over the lattice -- are stored once; proposed by a
+ *                         hash, decided by comparison, kept only where it saves at least half of the
+ *                         bricked bytes and fits the descriptors' 1 GiB; the product is bitwise the same;
+ *                         0 every row's own stream
+ *   "spmv_brick_dedup_full" 0, 1* [build]: a K whose rows are shared keeps the full 9-entry blocks -- read
+ *                         from the caches, the kernel is bound by its instructions and the compact stream's
+ *                         offsets cost more than its bytes save; the full layout is built first and the
+ *                         compact one only where the sharing is not taken; 0 the compact stream first
+ *   "spmv_brick_dedup_nt" 0* plain cached, 1 nontemporal as the full stream's [call]: value loads of a
+ *                         deduplicated K
+ *   "spmv_gather_wps"     0* by the runs per slice, 1, 2, 4 [call]: the run-mask gather's waves per 64-row
+ *                         slice
+ *
+ * Graph bricks and groups (the symmetric storage of an unstructured K)
+ *   "spmv_gsym_brick"     0, 1* [build]: graph K on graph bricks, whole rounds per CU; 0 the row groups
+ *   "spmv_gsym_rows"      8, 16, 32, 64*, 128 [build]: rows per group
+ *   "spmv_gsym_waves"     0* auto (16 for 64-row groups, else 8), 8, 16 [build]
+ *   "spmv_gsym_split"     >= 0, 0* auto [build]: the largest dictionary of the first of its two launches
+ *   "spmv_gsym_stpol"     0 plain, 1 nontemporal, 2* sc1, 3 sc0 sc1 [call]: the graph kernel's partial stores
+ *
+ * Assembly (these change stored values: not performance knobs)
+ *   "asm_box_uniform"     0, 1* [assembly]: on a box mesh every cell adds the blocks of global element 0's
+ *                         K_e and Rw_e into the free-slip K, Krhs and Rw, so rows that are translates of
+ *                         each other are the same bits and the brick SpMV stores them once; the values
+ *                         move by coordinate rounding, <= 1e-12 of the largest entry; 0 each cell's own
+ *                         matrix
+ *   "asm_box_zeros"       0, 1* [assembly]: an A/B and diagnosis switch: the free-slip K of a 3-D
+ *                         kle_mesh_create_box mesh stores its analytically zero block entries as +0.0 --
+ *                         entry (a, b), a != b, of the block between two nodes that share lattice
+ *                         coordinate a or b on a plane that is not a domain boundary plane; 0 the
+ *                         assembly's rounding noise there, a few 1e-16 of max|K|.  Every other entry, the
+ *                         pattern, Krhs, Rw, the operators, the no-slip matrices, 2-D and unstructured
+ *                         meshes are the same bits for both values
+ *
+ * CG
+ *   "ksp_refine"          0 .. 8, 2* [create]: correction solves of new KSPs (kle_ksp_set_corrections);
+ *                         0 PETSc's plain stop -- KLE_KSP_REFINE.  It changes what a solve returns
+ *   "upd_preload"         0, 1* [call]: CG update kernels load their first element and the stage inputs
+ *                         before the prologue
+ *   "upd_nt"              0 off, 1 on, 2* auto = from 2M local entries [call]: single-reduction CG update:
+ *                         every vector but u loaded and stored nontemporal, so u stays in the Infinity
+ *                         Cache for the SpMV
+ *   "upd_unroll"          1*, 2 [call]: elements per pass of the CG update kernel (2 only with "upd_preload" 1)
+ *   "ksp_pipe_gather"     0, 1* [call]: box bricks: the pipelined CG's update gathers the split product
+ *                         itself; 0 a separate gather launch
+ *   "ksp_sr_gather"       0 never, 1* from 2^17 node rows, 2 always [call]: the same for the
+ *                         single-reduction CG at one rank, the bricks forming (A u, u)
+ *
+ * Element-wise operators
+ *   "elem_ghost_rows"     0, 1* [call]: element-wise K, Krhs, Rw on several ranks: the ghost layer's GEMM
+ *                         over the row groups holding its top-plane rows alone; 0 every row group
+ *
+ * Debug and test hooks (not performance knobs)
+ *   "ipc_sentinel"        0*, 1 [call]: IPC transport debug mode: consumed mailbox slots overwritten with
+ *                         NaN before the ack
+ *   "ksp_corr_fault"      0*, 1 [call]: test hook: correction solves that end in NaN
+ *
+ * Not pure performance knobs: "ksp_corr_fault" and "ipc_sentinel" (hooks), "asm_box_zeros" and
+ * "asm_box_uniform" (stored values), "ksp_refine" (what a solve returns).  Every other value gives correct
+ * results.  The timing probes of the symmetric SpMV (keys spmv_sym_probe, spmv_sym_probe_ts: wrong results
+ * on purpose) exist only in the tools/ probe build, `make -C pynama_amd/csrc probe`. */
 int kle_set_tuning(const char *key, int value);
 int kle_get_tuning(const char *key, int *value);
 int kle_version(void);

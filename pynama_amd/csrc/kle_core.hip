@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -750,6 +751,80 @@ int kle_ctx::resolve_stats()
     return 0;
 }
 
+// ------------------------------------------------------------ tuning keys
+// One row per key, in the order of struct Tuning (kle_internal.hpp, where the
+// defaults and the measurements live): the field, the text a refusal prints
+// after the key's name, and the values kle_set_tuning accepts.
+template <int LO, int HI> static bool range(int v) { return v >= LO && v <= HI; }
+template <int... VS> static bool one_of(int v) { return ((v == VS) || ...); }
+static constexpr auto flag = range<0, 1>, from_0 = range<0, INT_MAX>;
+struct TuneKey {
+    const char *name;
+    int Tuning::*field;
+    const char *domain;
+    bool (*ok)(int);
+};
+#define KEY(field, domain, ...) {#field, &Tuning::field, domain, __VA_ARGS__}
+static const TuneKey tune_keys[] = {
+    KEY(spmv_waves, "0 (auto), 4 or 8", one_of<0, 4, 8>),
+    KEY(spmv_xcd_chunk, "0 (round-robin) or row blocks per XCD run", range<0, 4096>),
+    KEY(spmv_dyn_lds, "-1 (auto) or 0..65536 bytes", range<-1, 65536>),
+    KEY(ksp_sr_gather, "0, 1 or 2", range<0, 2>),
+    KEY(ksp_pipe_gather, "0 or 1", flag),
+    KEY(ipc_sentinel, "0 or 1", flag),
+    KEY(ksp_corr_fault, "0 or 1 (test hook)", flag),
+    KEY(ksp_refine, "0 .. 8", range<0, 8>),
+    KEY(upd_nt, "0 off, 1 on, 2 auto", range<0, 2>),
+    KEY(upd_preload, "0 or 1", flag),
+    KEY(spmv_x_lds, "0 or 1", flag),
+    KEY(spmv_sym, "0 or 1", flag),
+    KEY(spmv_sym_min_rows, ">= 0", from_0),
+    KEY(spmv_sym_det, "0 or 1", flag),
+    KEY(spmv_sym_waves, "0 (auto), 8 or 16", one_of<0, 8, 16>),
+    KEY(spmv_sym_align, "0 or 1", flag),
+    KEY(spmv_sym_tile64, "0 auto, 1 always, 2 never", range<0, 2>),
+    KEY(spmv_sym_tile64_max, ">= 0 tiles", from_0),
+    KEY(spmv_sym_xcd, "0 .. 4096 tiles", range<0, 4096>),
+    KEY(spmv_sym_ovl_b, "0 .. 100 ", range<0, 100>),  // (per cent; the text as it has always printed)
+    KEY(spmv_sym_stpol, "0 plain, 1 nt, 2 sc1, 3 sc0 sc1", range<0, 3>),
+    KEY(spmv_gsym_stpol, "0 plain, 1 nt, 2 sc1, 3 sc0 sc1", range<0, 3>),
+    KEY(spmv_sym_early, "0 or 1", flag),
+    KEY(spmv_sym_tz, "0 (auto), 2 or 4", one_of<0, 2, 4>),
+    KEY(spmv_brick_max, ">= 0 (0: one brick per CU)", from_0),
+    KEY(spmv_brick_rounds, "1 .. 4 bricks per CU", range<1, 4>),
+    KEY(upd_unroll, "1 or 2", range<1, 2>),
+    KEY(spmv_gsym_brick, "0 or 1", flag),
+    KEY(spmv_gather_wps, "0 (auto), 1, 2 or 4", one_of<0, 1, 2, 4>),
+    KEY(spmv_brick_compact, "0 or 1", flag),
+    KEY(spmv_brick_dedup, "0 or 1", flag),
+    KEY(spmv_brick_dedup_full, "0 or 1", flag),
+    KEY(spmv_brick_dedup_nt, "0 or 1", flag),
+    KEY(spmv_brick_pair, "0 or 1", flag),
+    KEY(spmv_brick_singles, "0 or 1", flag),
+    KEY(spmv_brick_split, "nbx + 100 nby + 10000 nbz (0: planned)", from_0),
+    KEY(elem_ghost_rows, "0 or 1", flag),
+    KEY(asm_box_uniform, "0 or 1", flag),
+    KEY(asm_box_zeros, "0 or 1", flag),
+    KEY(spmv_sym_brick, "0 (128-row tiles) or 1 (bricks)", flag),
+#ifdef KLE_PROBE_BUILD
+    KEY(spmv_sym_probe, "bit mask (< 4096) | ring slots << 12", from_0),
+#endif
+    KEY(spmv_gsym_rows, "8, 16, 32, 64 or 128", one_of<8, 16, 32, 64, 128>),
+    KEY(spmv_gsym_waves, "0, 8 or 16", one_of<0, 8, 16>),
+    KEY(spmv_gsym_split, ">= 0", from_0),
+    KEY(spmv_dict, "0 or 1", flag),
+    KEY(spmv_dict_min_rows, ">= 0", from_0),
+};
+#undef KEY
+// the key's row, or nullptr with the error set
+static const TuneKey *tune_key(const char *key)
+{
+    for (const TuneKey &t : tune_keys)
+        if (!strcmp(t.name, key)) return &t;
+    fail(KLE_ERR_ARG, "unknown tuning key '%s'", key);
+    return nullptr;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -758,118 +833,9 @@ const char *kle_last_error(void) { return g_err.c_str(); }
 int kle_set_tuning(const char *key, int value)
 {
     KLE_ARG(key, "null key");
-    const std::string k(key);
-    if (k == "spmv_waves") {
-        KLE_ARG(value == 0 || value == 4 || value == 8, "spmv_waves: 0 (auto), 4 or 8");
-        g_tune.spmv_waves = value;
-    } else if (k == "upd_nt") {
-        KLE_ARG(value >= 0 && value <= 2, "upd_nt: 0 off, 1 on, 2 auto");
-        g_tune.upd_nt = value;
-    } else if (k == "upd_preload") {
-        KLE_ARG(value == 0 || value == 1, "upd_preload: 0 or 1");
-        g_tune.upd_preload = value;
-    } else if (k == "spmv_dict") {
-        KLE_ARG(value == 0 || value == 1, "spmv_dict: 0 or 1");
-        g_tune.spmv_dict = value;
-    } else if (k == "spmv_dict_min_rows") {
-        KLE_ARG(value >= 0, "spmv_dict_min_rows: >= 0");
-        g_tune.spmv_dict_min_rows = value;
-    } else if (k == "spmv_sym") {
-        KLE_ARG(value == 0 || value == 1, "spmv_sym: 0 or 1");
-        g_tune.spmv_sym = value;
-    } else if (k == "spmv_sym_det") {
-        KLE_ARG(value == 0 || value == 1, "spmv_sym_det: 0 or 1");
-        g_tune.spmv_sym_det = value;
-    } else if (k == "spmv_sym_waves") {
-        KLE_ARG(value == 0 || value == 8 || value == 16, "spmv_sym_waves: 0 (auto), 8 or 16");
-        g_tune.spmv_sym_waves = value;
-    } else if (k == "spmv_sym_tile64") {
-        KLE_ARG(value >= 0 && value <= 2, "spmv_sym_tile64: 0 auto, 1 always, 2 never");
-        g_tune.spmv_sym_tile64 = value;
-    } else if (k == "spmv_sym_tile64_max") {
-        KLE_ARG(value >= 0, "spmv_sym_tile64_max: >= 0 tiles");
-        g_tune.spmv_sym_tile64_max = value;
-    } else if (k == "spmv_sym_xcd") {
-        KLE_ARG(value >= 0 && value <= 4096, "spmv_sym_xcd: 0 .. 4096 tiles");
-        g_tune.spmv_sym_xcd = value;
-    } else if (k == "spmv_sym_ovl_b") {
-        KLE_ARG(value >= 0 && value <= 100, "spmv_sym_ovl_b: 0 .. 100 %");
-        g_tune.spmv_sym_ovl_b = value;
-    } else if (k == "spmv_sym_stpol") {
-        KLE_ARG(value >= 0 && value <= 3, "spmv_sym_stpol: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1");
-        g_tune.spmv_sym_stpol = value;
-    } else if (k == "spmv_gsym_stpol") {
-        KLE_ARG(value >= 0 && value <= 3, "spmv_gsym_stpol: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1");
-        g_tune.spmv_gsym_stpol = value;
-    } else if (k == "spmv_sym_align") {
-        KLE_ARG(value == 0 || value == 1, "spmv_sym_align: 0 or 1");
-        g_tune.spmv_sym_align = value;
-    } else if (k == "spmv_sym_early") {
-        KLE_ARG(value == 0 || value == 1, "spmv_sym_early: 0 or 1");
-        g_tune.spmv_sym_early = value;
-        } else if (k == "upd_unroll") {
-        KLE_ARG(value == 1 || value == 2, "upd_unroll: 1 or 2");
-        g_tune.upd_unroll = value;
-    } else if (k == "spmv_gsym_brick") {
-        KLE_ARG(value == 0 || value == 1, "spmv_gsym_brick: 0 or 1");
-        g_tune.spmv_gsym_brick = value;
-        } else if (k == "spmv_brick_pair") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_pair: 0 or 1");
-        g_tune.spmv_brick_pair = value;
-    } else if (k == "spmv_brick_singles") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_singles: 0 or 1");
-        g_tune.spmv_brick_singles = value;
-    } else if (k == "elem_ghost_rows") {
-        KLE_ARG(value == 0 || value == 1, "elem_ghost_rows: 0 or 1");
-        g_tune.elem_ghost_rows = value;
-                        } else if (k == "spmv_gather_wps") {
-        KLE_ARG(value == 0 || value == 1 || value == 2 || value == 4, "spmv_gather_wps: 0 (auto), 1, 2 or 4");
-        g_tune.spmv_gather_wps = value;
-                } else if (k == "spmv_brick_split") {
-        KLE_ARG(value >= 0, "spmv_brick_split: nbx + 100 nby + 10000 nbz (0: planned)");
-        g_tune.spmv_brick_split = value;
-    } else if (k == "spmv_brick_rounds") {
-        KLE_ARG(value >= 1 && value <= 4, "spmv_brick_rounds: 1 .. 4 bricks per CU");
-        g_tune.spmv_brick_rounds = value;
-    } else if (k == "spmv_brick_max") {
-        KLE_ARG(value >= 0, "spmv_brick_max: >= 0 (0: one brick per CU)");
-        g_tune.spmv_brick_max = value;
-    } else if (k == "spmv_sym_brick") {
-        KLE_ARG(value == 0 || value == 1, "spmv_sym_brick: 0 (128-row tiles) or 1 (bricks)");
-        g_tune.spmv_sym_brick = value;
-    } else if (k == "spmv_sym_tz") {
-        KLE_ARG(value == 0 || value == 2 || value == 4, "spmv_sym_tz: 0 (auto), 2 or 4");
-        g_tune.spmv_sym_tz = value;
-    } else if (k == "ksp_pipe_gather") {
-        KLE_ARG(value == 0 || value == 1, "ksp_pipe_gather: 0 or 1");
-        g_tune.ksp_pipe_gather = value;
-    } else if (k == "ksp_sr_gather") {
-        KLE_ARG(value >= 0 && value <= 2, "ksp_sr_gather: 0, 1 or 2");
-        g_tune.ksp_sr_gather = value;
-    } else if (k == "ipc_sentinel") {
-        KLE_ARG(value == 0 || value == 1, "ipc_sentinel: 0 or 1");
-        g_tune.ipc_sentinel = value;
-    } else if (k == "ksp_corr_fault") {
-        KLE_ARG(value == 0 || value == 1, "ksp_corr_fault: 0 or 1 (test hook)");
-        g_tune.ksp_corr_fault = value;
-    } else if (k == "ksp_refine") {
-        KLE_ARG(value >= 0 && value <= 8, "ksp_refine: 0 .. 8");
-        g_tune.ksp_refine = value;
-    } else if (k == "spmv_gsym_rows") {
-        KLE_ARG(value == 8 || value == 16 || value == 32 || value == 64 || value == 128,
-                "spmv_gsym_rows: 8, 16, 32, 64 or 128");
-        g_tune.spmv_gsym_rows = value;
-    } else if (k == "spmv_gsym_waves") {
-        KLE_ARG(value == 0 || value == 8 || value == 16, "spmv_gsym_waves: 0, 8 or 16");
-        g_tune.spmv_gsym_waves = value;
-    } else if (k == "spmv_gsym_split") {
-        KLE_ARG(value >= 0, "spmv_gsym_split: >= 0");
-        g_tune.spmv_gsym_split = value;
 #ifdef KLE_PROBE_BUILD
-    } else if (k == "spmv_sym_probe") {
-        KLE_ARG(value >= 0, "spmv_sym_probe: bit mask (< 4096) | ring slots << 12");
-        g_tune.spmv_sym_probe = value;
-    } else if (k == "spmv_sym_probe_ts") {
+    // set-only, and it allocates: the probe build's timestamp slots
+    if (!strcmp(key, "spmv_sym_probe_ts")) {
         KLE_ARG(value >= 0, "spmv_sym_probe_ts: workgroup slots (0: off)");
         if (g_probe_ts) (void)hipFree(g_probe_ts);
         g_probe_ts = nullptr;
@@ -879,40 +845,13 @@ int kle_set_tuning(const char *key, int value)
             KLE_HIP(hipMemset(g_probe_ts, 0, sizeof(unsigned long long) * 8 * (size_t)value));
             g_probe_ts_cap = value;
         }
-#endif
-    } else if (k == "spmv_brick_compact") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_compact: 0 or 1");
-        g_tune.spmv_brick_compact = value;
-    } else if (k == "spmv_brick_dedup") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup: 0 or 1");
-        g_tune.spmv_brick_dedup = value;
-    } else if (k == "spmv_brick_dedup_full") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup_full: 0 or 1");
-        g_tune.spmv_brick_dedup_full = value;
-    } else if (k == "spmv_brick_dedup_nt") {
-        KLE_ARG(value == 0 || value == 1, "spmv_brick_dedup_nt: 0 or 1");
-        g_tune.spmv_brick_dedup_nt = value;
-    } else if (k == "asm_box_uniform") {
-        KLE_ARG(value == 0 || value == 1, "asm_box_uniform: 0 or 1");
-        g_tune.asm_box_uniform = value;
-    } else if (k == "asm_box_zeros") {
-        KLE_ARG(value == 0 || value == 1, "asm_box_zeros: 0 or 1");
-        g_tune.asm_box_zeros = value;
-    } else if (k == "spmv_sym_min_rows") {
-        KLE_ARG(value >= 0, "spmv_sym_min_rows: >= 0");
-        g_tune.spmv_sym_min_rows = value;
-    } else if (k == "spmv_x_lds") {
-        KLE_ARG(value == 0 || value == 1, "spmv_x_lds: 0 or 1");
-        g_tune.spmv_x_lds = value;
-    } else if (k == "spmv_xcd_chunk") {
-        KLE_ARG(value >= 0 && value <= 4096, "spmv_xcd_chunk: 0 (round-robin) or row blocks per XCD run");
-        g_tune.spmv_xcd_chunk = value;
-    } else if (k == "spmv_dyn_lds") {
-        KLE_ARG(value >= -1 && value <= 65536, "spmv_dyn_lds: -1 (auto) or 0..65536 bytes");
-        g_tune.spmv_dyn_lds = value;
-    } else {
-        return fail(KLE_ERR_ARG, "unknown tuning key '%s'", key);
+        return 0;
     }
+#endif
+    const TuneKey *t = tune_key(key);
+    if (!t) return KLE_ERR_ARG;
+    KLE_ARG(t->ok(value), "%s: %s", t->name, t->domain);
+    g_tune.*t->field = value;
     return 0;
 }
 
@@ -930,56 +869,9 @@ extern "C" int kle_probe_timestamps(unsigned long long *out, int64_t slots)
 int kle_get_tuning(const char *key, int *value)
 {
     KLE_ARG(key && value, "null arg");
-    const std::string k(key);
-    if (k == "spmv_waves") *value = g_tune.spmv_waves;
-    else if (k == "spmv_dyn_lds") *value = g_tune.spmv_dyn_lds;
-    else if (k == "spmv_xcd_chunk") *value = g_tune.spmv_xcd_chunk;
-    else if (k == "spmv_x_lds") *value = g_tune.spmv_x_lds;
-    else if (k == "spmv_dict") *value = g_tune.spmv_dict;
-    else if (k == "upd_preload") *value = g_tune.upd_preload;
-    else if (k == "upd_nt") *value = g_tune.upd_nt;
-    else if (k == "spmv_dict_min_rows") *value = g_tune.spmv_dict_min_rows;
-    else if (k == "spmv_sym") *value = g_tune.spmv_sym;
-    else if (k == "spmv_sym_det") *value = g_tune.spmv_sym_det;
-    else if (k == "spmv_sym_waves") *value = g_tune.spmv_sym_waves;
-    else if (k == "spmv_sym_tz") *value = g_tune.spmv_sym_tz;
-    else if (k == "spmv_sym_brick") *value = g_tune.spmv_sym_brick;
-    else if (k == "spmv_brick_max") *value = g_tune.spmv_brick_max;
-    else if (k == "spmv_brick_rounds") *value = g_tune.spmv_brick_rounds;
-    else if (k == "spmv_brick_split") *value = g_tune.spmv_brick_split;
-    else if (k == "spmv_brick_singles") *value = g_tune.spmv_brick_singles;
-    else if (k == "spmv_brick_pair") *value = g_tune.spmv_brick_pair;
-    else if (k == "elem_ghost_rows") *value = g_tune.elem_ghost_rows;
-    else if (k == "asm_box_zeros") *value = g_tune.asm_box_zeros;
-    else if (k == "asm_box_uniform") *value = g_tune.asm_box_uniform;
-    else if (k == "spmv_brick_compact") *value = g_tune.spmv_brick_compact;
-    else if (k == "spmv_brick_dedup") *value = g_tune.spmv_brick_dedup;
-    else if (k == "spmv_brick_dedup_nt") *value = g_tune.spmv_brick_dedup_nt;
-    else if (k == "spmv_brick_dedup_full") *value = g_tune.spmv_brick_dedup_full;
-    else if (k == "spmv_gather_wps") *value = g_tune.spmv_gather_wps;
-    else if (k == "spmv_gsym_brick") *value = g_tune.spmv_gsym_brick;
-    else if (k == "upd_unroll") *value = g_tune.upd_unroll;
-    else if (k == "spmv_sym_early") *value = g_tune.spmv_sym_early;
-    else if (k == "spmv_sym_align") *value = g_tune.spmv_sym_align;
-    else if (k == "spmv_sym_stpol") *value = g_tune.spmv_sym_stpol;
-    else if (k == "spmv_gsym_stpol") *value = g_tune.spmv_gsym_stpol;
-    else if (k == "spmv_sym_ovl_b") *value = g_tune.spmv_sym_ovl_b;
-    else if (k == "spmv_sym_xcd") *value = g_tune.spmv_sym_xcd;
-    else if (k == "spmv_sym_tile64") *value = g_tune.spmv_sym_tile64;
-    else if (k == "spmv_sym_tile64_max") *value = g_tune.spmv_sym_tile64_max;
-#ifdef KLE_PROBE_BUILD
-    else if (k == "spmv_sym_probe") *value = g_tune.spmv_sym_probe;
-#endif
-    else if (k == "spmv_gsym_rows") *value = g_tune.spmv_gsym_rows;
-    else if (k == "ksp_refine") *value = g_tune.ksp_refine;
-    else if (k == "ksp_corr_fault") *value = g_tune.ksp_corr_fault;
-    else if (k == "ipc_sentinel") *value = g_tune.ipc_sentinel;
-    else if (k == "ksp_pipe_gather") *value = g_tune.ksp_pipe_gather;
-    else if (k == "ksp_sr_gather") *value = g_tune.ksp_sr_gather;
-    else if (k == "spmv_gsym_split") *value = g_tune.spmv_gsym_split;
-    else if (k == "spmv_gsym_waves") *value = g_tune.spmv_gsym_waves;
-    else if (k == "spmv_sym_min_rows") *value = g_tune.spmv_sym_min_rows;
-    else return fail(KLE_ERR_ARG, "unknown tuning key '%s'", key);
+    const TuneKey *t = tune_key(key);
+    if (!t) return KLE_ERR_ARG;
+    *value = g_tune.*t->field;
     return 0;
 }
 int kle_version(void) { return 1; }

@@ -478,8 +478,10 @@ int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t>
 std::string sym_kernel_name(const kle_mat *A);
 double sym_spmv_bytes(const kle_mat *A);
 double brick_split_bytes(const kle_mat *A);  // a split brick product: the bricks alone
-// Performance knobs (kle_set_tuning): every setting gives correct results;
-// they exist for in-process A/B measurements (tools/cg_ab.py).
+// Tuning keys (kle_set_tuning) for in-process A/B measurements (tools/cg_ab.py):
+// the defaults and the measurements behind them.  Each field has one row of
+// tune_keys (kle_core.hip) and one entry of the list in include/kle.h, which
+// names the few keys that are not pure performance knobs.
 struct Tuning {
     int spmv_waves = 0;  // rows per SpMV workgroup for 3x3 chunked matrices: 0 auto (8 from 64k rows, else 4), 4, 8
     int spmv_xcd_chunk = 16;  // SpMV: consecutive row blocks per XCD in each run (0: round-robin), xcd_block()

@@ -1096,6 +1096,7 @@ struct kle_ksp {
     double rtol = 1e-5, atol = 1e-50, dtol = 1e5;
     int maxit = 10000, restart = 30, fixed = 0, check_every = 8;
     int pipe_par = 0;  // pipelined CG: parity of the next update launch (k_pipe_iter)
+    int istate0[I_COUNT] = {};  // the iteration state a CG call starts from, as uploaded (solve_begin)
     std::string prod_kernel;  // the kernel(s) of the last call's products (kle_ksp_get_product_kernel)
     double prod_bytes = 0.0;  // and the algorithmic bytes each moves (kle_ksp_get_product_bytes)
     kle_mat *A = nullptr;
@@ -1285,6 +1286,42 @@ static int put_dtol(kle_ksp *k)
     return 0;
 }
 
+// The frame the three CG solvers share.  solve_begin: the iteration state of
+// a call (its count from 0, the fixed count, the limit) onto the device.
+static int solve_begin(kle_ksp *k)
+{
+    kle_ctx *c = k->ctx;
+    const int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
+    std::copy(host_fixed, host_fixed + I_COUNT, k->istate0);  // (an asynchronous copy's source outlives this frame)
+    KLE_HIP(hipMemcpyAsync(c->d_istate, k->istate0, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// solve_end: the call's outcome off the device
+static int solve_end(kle_ksp *k)
+{
+    kle_ctx *c = k->ctx;
+    KLE_TRY(poll_state(k));
+    k->its = c->h_istate[I_ITS];
+    k->reason = c->h_istate[I_REASON];
+    if (k->reason == 0) k->reason = k->fixed ? KLE_CONVERGED_ITS : KLE_DIVERGED_ITS;
+    k->rnorm = std::sqrt(c->h_scal[S_RR]);
+    return 0;
+}
+
+// A statement for the preconditioner at hand: inside it JAC is the constant
+// true with Jacobi, else false -- WITH_JAC(jac, launch(k_cg_p<JAC>, ...))
+#define WITH_JAC(jac, ...)                                                               \
+    do {                                                                                 \
+        if (jac) {                                                                       \
+            constexpr bool JAC = true;                                                   \
+            __VA_ARGS__;                                                                 \
+        } else {                                                                         \
+            constexpr bool JAC = false;                                                  \
+            __VA_ARGS__;                                                                 \
+        }                                                                                \
+    } while (0)
+
 static int solve_cg(kle_ksp *k, kle_vec *b, kle_vec *x)
 {
     kle_ctx *c = k->ctx;
@@ -1292,37 +1329,24 @@ static int solve_cg(kle_ksp *k, kle_vec *b, kle_vec *x)
     const bool jac = k->pc == "jacobi";
     const double *dinv = jac ? k->dinv->d : nullptr;
     const int g = grid_for(n, KB, RED_BLOCKS);
-    int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
-    KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
+    KLE_TRY(solve_begin(k));
     KLE_TRY(put_dtol(k));
-    if (jac)
-        hipLaunchKernelGGL(k_cg_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d, k->p->d,
-                           c->d_partials);
-    else
-        hipLaunchKernelGGL(k_cg_start<false>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d, k->p->d,
-                           c->d_partials);
+    WITH_JAC(jac, hipLaunchKernelGGL(k_cg_start<JAC>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
+                                     k->p->d, c->d_partials));
     KLE_HIP(hipGetLastError());
     KLE_TRY(reduce_stage(k, NParts{{g, g, 0, 0}}, 2, ST_START));
     const int limit = k->fixed ? k->fixed : k->maxit;
     std::pair<hipEvent_t, hipEvent_t> ev;
     for (int it = 0; it < limit; ++it) {
         KLE_TRY(c->tic("p_update", &ev));
-        if (jac)
-            hipLaunchKernelGGL(k_cg_p<true>, dim3(g), dim3(KB), 0, c->stream, n, k->r->d, dinv, k->p->d, c->d_scal,
-                               c->d_istate);
-        else
-            hipLaunchKernelGGL(k_cg_p<false>, dim3(g), dim3(KB), 0, c->stream, n, k->r->d, dinv, k->p->d, c->d_scal,
-                               c->d_istate);
+        WITH_JAC(jac, hipLaunchKernelGGL(k_cg_p<JAC>, dim3(g), dim3(KB), 0, c->stream, n, k->r->d, dinv, k->p->d,
+                                         c->d_scal, c->d_istate));
         KLE_HIP(hipGetLastError());
         KLE_TRY(c->toc("p_update", &ev));
         KLE_TRY(spmv_finish(k, k->p, k->q, 0, 0, ST_ALPHA, c->d_istate));
         KLE_TRY(c->tic("cg_update", &ev));
-        if (jac)
-            hipLaunchKernelGGL(k_cg_update<true>, dim3(g), dim3(KB), 0, c->stream, n, k->p->d, k->q->d, dinv, x->d,
-                               k->r->d, c->d_partials, c->d_scal, c->d_istate);
-        else
-            hipLaunchKernelGGL(k_cg_update<false>, dim3(g), dim3(KB), 0, c->stream, n, k->p->d, k->q->d, dinv, x->d,
-                               k->r->d, c->d_partials, c->d_scal, c->d_istate);
+        WITH_JAC(jac, hipLaunchKernelGGL(k_cg_update<JAC>, dim3(g), dim3(KB), 0, c->stream, n, k->p->d, k->q->d, dinv,
+                                         x->d, k->r->d, c->d_partials, c->d_scal, c->d_istate));
         KLE_HIP(hipGetLastError());
         KLE_TRY(c->toc("cg_update", &ev));
         KLE_TRY(reduce_stage(k, NParts{{g, g, 0, 0}}, 2, ST_BETA));
@@ -1331,12 +1355,7 @@ static int solve_cg(kle_ksp *k, kle_vec *b, kle_vec *x)
             if (c->h_istate[I_REASON] != 0) break;
         }
     }
-    KLE_TRY(poll_state(k));
-    k->its = c->h_istate[I_ITS];
-    k->reason = c->h_istate[I_REASON];
-    if (k->reason == 0) k->reason = k->fixed ? KLE_CONVERGED_ITS : KLE_DIVERGED_ITS;
-    k->rnorm = std::sqrt(c->h_scal[S_RR]);
-    return 0;
+    return solve_end(k);
 }
 
 // The kernel names a solve's products launch, as rocprof lists them: the
@@ -1361,8 +1380,25 @@ static std::string split_kernel_name(const kle_mat *A, bool dot)
     if (dist) return m;
     const size_t plus = m.find('+');
     std::string b = plus == std::string::npos ? m : m.substr(0, plus);
-    if (dot) b.replace(b.rfind("false>"), 6, "true>");
+    const size_t f = dot ? b.rfind("false>") : std::string::npos;
+    if (f != std::string::npos) b.replace(f, 6, "true>");
     return b;
+}
+
+// The start the single-reduction and the pipelined CG share: r, u, p, s from
+// b and x, then w = A u with (w, u) and the first scalars
+static int sr_start(kle_ksp *k, kle_vec *b, kle_vec *x)
+{
+    kle_ctx *c = k->ctx;
+    const int64_t n = b->n_local;
+    const bool jac = k->pc == "jacobi";
+    const double *dinv = jac ? k->dinv->d : nullptr;
+    const int g = grid_for(n, KB, RED_BLOCKS);
+    KLE_TRY(put_dtol(k));
+    WITH_JAC(jac, hipLaunchKernelGGL(k_sr_start<JAC>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
+                                     k->u->d, k->p->d, k->s->d, c->d_partials));
+    KLE_HIP(hipGetLastError());
+    return spmv_finish(k, k->u, k->w, 2, g, ST_SR_START, nullptr);
 }
 
 // Chronopoulos-Gear CG (PETSc -ksp_cg_single_reduction): one fused update
@@ -1375,32 +1411,19 @@ static int solve_cg_single(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     const int64_t n = b->n_local;
     const bool jac = k->pc == "jacobi";
     const double *dinv = jac ? k->dinv->d : nullptr;
-    const int g = grid_for(n, KB, RED_BLOCKS);
-    int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
-    KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
-    if (!cont) {
-        KLE_TRY(put_dtol(k));
-        if (jac)
-            hipLaunchKernelGGL(k_sr_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
-                               k->u->d, k->p->d, k->s->d, c->d_partials);
-        else
-            hipLaunchKernelGGL(k_sr_start<false>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
-                               k->u->d, k->p->d, k->s->d, c->d_partials);
-        KLE_HIP(hipGetLastError());
-        KLE_TRY(spmv_finish(k, k->u, k->w, 2, g, ST_SR_START, nullptr));
-    }
+    KLE_TRY(solve_begin(k));
+    if (!cont) KLE_TRY(sr_start(k, b, x));
     const int limit = k->fixed ? k->fixed : k->maxit;
     std::pair<hipEvent_t, hipEvent_t> ev;
-    // pro_mode (default): the scalar stage runs in the next update's prologue
-    // (k_sr_iter) and the (w, u) dot is a plain partial launch -- no
-    // last-arriver ticket, no scalar kernel (as the pipelined CG, §3).  Per
+    // The scalar stage runs in the next update's prologue (k_sr_iter) and the
+    // (w, u) dot is a plain partial launch -- no last-arriver ticket, no
+    // scalar kernel (as the pipelined CG, §3; the only form left).  Per
     // parity one buffer [2][G] update partials | [Gd] dot partials; on N ranks
     // (or a one-rank RCCL communicator) it is allreduced as one array after
     // the dot (G, Gd equal on every rank), then the next prologue reads it.  A
     // flush closes the call.  Against update + SpMV + k_dot_finish (last-
     // arriver sum + stage): config 2 782.3 vs 782.3 us per iteration, 1/8
     // slab 85.65 vs 88.29 (profiles/r02/sr_prologue_*.jsonl).
-    const bool pro_mode = true;
     const bool fuse = c->nranks == 1 && !c->comm;
     // grids capped at 1024 update / 512 dot workgroups: every prologue reads
     // all 2 Gu + Gd partials (config 2: 788.5 vs 792.4 us per iteration with
@@ -1424,7 +1447,7 @@ static int solve_cg_single(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     bool npend = false;
     k->prod_kernel = gfuse ? split_kernel_name(k->A, true) : mat_kernel_name(k->A);
     k->prod_bytes = gfuse ? brick_split_bytes(k->A) : mat_bytes(k->A);
-    if (pro_mode && c->nranks > 1) {
+    if (c->nranks > 1) {
         std::vector<int64_t> all;
         KLE_TRY(allgather_i64(c, ((int64_t)Gu << 20) | Gd, all));
         for (int64_t v : all) {
@@ -1437,64 +1460,55 @@ static int solve_cg_single(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     if (!cont) k->pipe_par = 0;
     int par = k->pipe_par;
     bool pending = false;  // an update's partials await the next launch's prologue
-    auto iteration = [&]() -> int {
-        KLE_TRY(c->tic("cg_update", &ev));
-        {
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(Gu), dim3(KB), 0, c->stream, n, dinv, k->w->d, k->u->d, k->p->d,
-                                   k->s->d, x->d, k->r->d, pu[par], pu[par] + 2 * Gu, Gd, pu[par ^ 1], c->d_scal,
-                                   c->d_istate, (int)pending, par, k->atol);
-            };
-            auto gog = [&](auto kern) {
-                BrickGather gs = brick_gather_src(k->A, k->u);
-                if (!npend) gs.ng = 0;  // (w complete: read it)
-                hipLaunchKernelGGL(kern, dim3(Gu), dim3(KB), 0, c->stream, gs, n, dinv, k->w->d, k->u->d, k->p->d,
-                                   k->s->d, x->d, k->r->d, pu[par], Gd, pu[par ^ 1], c->d_scal, c->d_istate,
-                                   (int)pending, par, k->atol);
-            };
-            const bool unr = g_tune.upd_unroll == 2 && g_tune.upd_preload;
-            if (gfuse) {
-                // (w complete -- the first update of a call -- the same
-                // kernel reads it: W + n iterations equal one call, bitwise)
-                if (jac) gog(g_tune.upd_preload ? k_sr_iter_g<true, true> : k_sr_iter_g<true, false>);
-                else gog(g_tune.upd_preload ? k_sr_iter_g<false, true> : k_sr_iter_g<false, false>);
-                npend = false;
-            } else if (jac && (g_tune.upd_nt == 1 || (g_tune.upd_nt == 2 && n >= 2000000)))
-                go(unr ? k_sr_iter<true, true, true, 2> : g_tune.upd_preload ? k_sr_iter<true, true, true> : k_sr_iter<true, false, true>);
-            else if (jac) go(unr ? k_sr_iter<true, true, false, 2> : g_tune.upd_preload ? k_sr_iter<true, true> : k_sr_iter<true, false>);
-            else go(g_tune.upd_preload ? k_sr_iter<false, true> : k_sr_iter<false, false>);
-            KLE_HIP(hipGetLastError());
-            KLE_TRY(c->toc("cg_update", &ev));
-            par ^= 1;
-            pending = true;
-            int nd = 0;
-            if (gfuse) {
-                KLE_TRY(spmv_split(k->A, k->u, k->w, c->d_istate, pu[par] + 3 * Gu));
-                npend = true;
-                nd = Gd;  // (the update's one-block share + the bricks')
-            } else if (Gd == Gf) KLE_TRY(spmv_dot(k->A, k->u, k->w, c->d_istate, pu[par] + 2 * Gu, &nd));
-            else KLE_TRY(spmv(k->A, k->u, k->w, c->d_istate));
-            if (nd != Gd) {
-                KLE_TRY(c->tic("reduce", &ev));
-                hipLaunchKernelGGL(k_dot_part, dim3(Gd), dim3(KB), 0, c->stream, n, k->u->d, k->w->d,
-                                   pu[par] + 2 * Gu, c->d_istate);
-                KLE_HIP(hipGetLastError());
-                KLE_TRY(c->toc("reduce", &ev));
-            }
-            if (!fuse) KLE_TRY(allreduce_sum(c, pu[par], 2 * Gu + Gd));
-            return 0;
-        }
-        return 0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(Gu), dim3(KB), 0, c->stream, n, dinv, k->w->d, k->u->d, k->p->d, k->s->d, x->d,
+                           k->r->d, pu[par], pu[par] + 2 * Gu, Gd, pu[par ^ 1], c->d_scal, c->d_istate, (int)pending,
+                           par, k->atol);
     };
-    int it = 0;
-    for (; it < limit; ++it) {
-        KLE_TRY(iteration());
+    auto gog = [&](auto kern) {
+        BrickGather gs = brick_gather_src(k->A, k->u);
+        if (!npend) gs.ng = 0;  // (w complete: read it)
+        hipLaunchKernelGGL(kern, dim3(Gu), dim3(KB), 0, c->stream, gs, n, dinv, k->w->d, k->u->d, k->p->d, k->s->d,
+                           x->d, k->r->d, pu[par], Gd, pu[par ^ 1], c->d_scal, c->d_istate, (int)pending, par,
+                           k->atol);
+    };
+    const bool unr = g_tune.upd_unroll == 2 && g_tune.upd_preload;
+    for (int it = 0; it < limit; ++it) {
+        KLE_TRY(c->tic("cg_update", &ev));
+        if (gfuse) {
+            // (w complete -- the first update of a call -- the same
+            // kernel reads it: W + n iterations equal one call, bitwise)
+            WITH_JAC(jac, gog(g_tune.upd_preload ? k_sr_iter_g<JAC, true> : k_sr_iter_g<JAC, false>));
+            npend = false;
+        } else if (jac && (g_tune.upd_nt == 1 || (g_tune.upd_nt == 2 && n >= 2000000)))
+            go(unr ? k_sr_iter<true, true, true, 2> : g_tune.upd_preload ? k_sr_iter<true, true, true> : k_sr_iter<true, false, true>);
+        else if (jac) go(unr ? k_sr_iter<true, true, false, 2> : g_tune.upd_preload ? k_sr_iter<true, true> : k_sr_iter<true, false>);
+        else go(g_tune.upd_preload ? k_sr_iter<false, true> : k_sr_iter<false, false>);
+        KLE_HIP(hipGetLastError());
+        KLE_TRY(c->toc("cg_update", &ev));
+        par ^= 1;
+        pending = true;
+        int nd = 0;
+        if (gfuse) {
+            KLE_TRY(spmv_split(k->A, k->u, k->w, c->d_istate, pu[par] + 3 * Gu));
+            npend = true;
+            nd = Gd;  // (the update's one-block share + the bricks')
+        } else if (Gd == Gf) KLE_TRY(spmv_dot(k->A, k->u, k->w, c->d_istate, pu[par] + 2 * Gu, &nd));
+        else KLE_TRY(spmv(k->A, k->u, k->w, c->d_istate));
+        if (nd != Gd) {
+            KLE_TRY(c->tic("reduce", &ev));
+            hipLaunchKernelGGL(k_dot_part, dim3(Gd), dim3(KB), 0, c->stream, n, k->u->d, k->w->d, pu[par] + 2 * Gu,
+                               c->d_istate);
+            KLE_HIP(hipGetLastError());
+            KLE_TRY(c->toc("reduce", &ev));
+        }
+        if (!fuse) KLE_TRY(allreduce_sum(c, pu[par], 2 * Gu + Gd));
         if (!k->fixed && ((it + 1) % k->check_every == 0)) {
             KLE_TRY(poll_state(k));
             if (c->h_istate[I_REASON] != 0) break;
         }
     }
-    if (pro_mode && pending) {
+    if (pending) {
         hipLaunchKernelGGL(k_cg_flush, dim3(1), dim3(KB), 0, c->stream, pu[par], pu[par] + Gu, Gu, pu[par] + 2 * Gu,
                            Gd, c->d_scal, c->d_istate, par, k->atol);
         KLE_HIP(hipGetLastError());
@@ -1502,14 +1516,23 @@ static int solve_cg_single(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     // (w complete when the call returns: a continuation's first update reads it)
     if (npend) KLE_TRY(brick_gather_rest(k->A, k->u, k->w, c->d_istate, 1));
     k->pipe_par = par;
-    KLE_TRY(poll_state(k));
-    k->its = c->h_istate[I_ITS];
-    k->reason = c->h_istate[I_REASON];
-    if (k->reason == 0) k->reason = k->fixed ? KLE_CONVERGED_ITS : KLE_DIVERGED_ITS;
-    k->rnorm = std::sqrt(c->h_scal[S_RR]);
-    return 0;
+    return solve_end(k);
 }
 
+
+// an event of one call's own, destroyed on every way out of it
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent &) = delete;
+    OwnedEvent &operator=(const OwnedEvent &) = delete;
+    void reset()
+    {
+        if (e) hipEventDestroy(e);
+        e = nullptr;
+    }
+    ~OwnedEvent() { reset(); }
+};
 
 // Pipelined CG (PETSc KSPPIPECG): the reduction of iteration i (and its
 // allreduce across ranks) runs on the comm stream while the SpMV n = A m of
@@ -1521,25 +1544,11 @@ static int solve_pipecg(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     const int64_t n = b->n_local;
     const bool jac = k->pc == "jacobi";
     const double *dinv = jac ? k->dinv->d : nullptr;
-    const int g = grid_for(n, KB, RED_BLOCKS);
-    int host_fixed[I_COUNT] = {0, 0, k->fixed, k->fixed ? k->fixed : k->maxit, 0, 0, 0, 0};
-    KLE_HIP(hipMemcpyAsync(c->d_istate, host_fixed, sizeof(int) * I_COUNT, hipMemcpyHostToDevice, c->stream));
+    KLE_TRY(solve_begin(k));
     if (!cont) {
-        KLE_TRY(put_dtol(k));
-        if (jac)
-            hipLaunchKernelGGL(k_sr_start<true>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
-                               k->u->d, k->p->d, k->s->d, c->d_partials);
-        else
-            hipLaunchKernelGGL(k_sr_start<false>, dim3(g), dim3(KB), 0, c->stream, n, b->d, dinv, x->d, k->r->d,
-                               k->u->d, k->p->d, k->s->d, c->d_partials);
-        KLE_HIP(hipGetLastError());
-        KLE_TRY(spmv_finish(k, k->u, k->w, 2, g, ST_SR_START, nullptr));  // w = A u, (w,u), scalars
-        if (jac)
-            hipLaunchKernelGGL(k_pipe_init<true>, dim3(g), dim3(KB), 0, c->stream, n, dinv, k->w->d, k->m->d,
-                               k->z->d, k->q->d);
-        else
-            hipLaunchKernelGGL(k_pipe_init<false>, dim3(g), dim3(KB), 0, c->stream, n, dinv, k->w->d, k->m->d,
-                               k->z->d, k->q->d);
+        KLE_TRY(sr_start(k, b, x));  // w = A u, (w,u), scalars
+        WITH_JAC(jac, hipLaunchKernelGGL(k_pipe_init<JAC>, dim3(grid_for(n, KB, RED_BLOCKS)), dim3(KB), 0, c->stream,
+                                         n, dinv, k->w->d, k->m->d, k->z->d, k->q->d));
         KLE_HIP(hipGetLastError());
     }
     // box bricks: each product n = A m leaves its owned rows' gather to the
@@ -1573,46 +1582,40 @@ static int solve_pipecg(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
     if (!cont) k->pipe_par = 0;
     int par = k->pipe_par;
     bool pending = false;  // a launch's partials await the next launch's prologue
-    hipEvent_t ev_red = nullptr;
-    KLE_HIP(hipEventCreateWithFlags(&ev_red, sync_event_flags()));
+    OwnedEvent ev_red;
+    KLE_HIP(hipEventCreateWithFlags(&ev_red.e, sync_event_flags()));
     const int limit = k->fixed ? k->fixed : k->maxit;
     std::pair<hipEvent_t, hipEvent_t> ev;
-    int rc = 0;
-    for (int it = 0; it < limit && !rc; ++it) {
-        rc = c->tic("cg_update", &ev);
-        if (rc) break;
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(G), dim3(KB), 0, c->stream, n, dinv, k->nv->d, k->z->d, k->q->d, k->s->d,
-                               k->p->d, x->d, k->r->d, k->u->d, k->w->d, k->m->d, pp[par], pp[par ^ 1], c->d_scal,
-                               c->d_istate, (int)pending, par, k->atol);
-        };
-        auto gog = [&](auto kern) {
-            BrickGather gs = brick_gather_src(k->A, k->m);
-            if (!npend) gs.ng = gs.nrecv = 0;  // (n complete: read it)
-            hipLaunchKernelGGL(kern, dim3(G), dim3(KB), 0, c->stream, gs, n, dinv,
-                               k->nv->d, k->z->d, k->q->d, k->s->d, k->p->d, x->d, k->r->d, k->u->d, k->w->d,
-                               k->m->d, pp[par], pp[par ^ 1], c->d_scal, c->d_istate, (int)pending, par, k->atol);
-        };
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(G), dim3(KB), 0, c->stream, n, dinv, k->nv->d, k->z->d, k->q->d, k->s->d,
+                           k->p->d, x->d, k->r->d, k->u->d, k->w->d, k->m->d, pp[par], pp[par ^ 1], c->d_scal,
+                           c->d_istate, (int)pending, par, k->atol);
+    };
+    auto gog = [&](auto kern) {
+        BrickGather gs = brick_gather_src(k->A, k->m);
+        if (!npend) gs.ng = gs.nrecv = 0;  // (n complete: read it)
+        hipLaunchKernelGGL(kern, dim3(G), dim3(KB), 0, c->stream, gs, n, dinv, k->nv->d, k->z->d, k->q->d, k->s->d,
+                           k->p->d, x->d, k->r->d, k->u->d, k->w->d, k->m->d, pp[par], pp[par ^ 1], c->d_scal,
+                           c->d_istate, (int)pending, par, k->atol);
+    };
+    for (int it = 0; it < limit; ++it) {
+        KLE_TRY(c->tic("cg_update", &ev));
         if (gfuse) {
             // (n complete -- the first update of a continued call -- the
             // same kernel reads it: the same arithmetic in the same order as
             // one uninterrupted solve, bitwise)
-            if (jac) gog(k_pipe_iter_g<true>);
-            else gog(k_pipe_iter_g<false>);
+            WITH_JAC(jac, gog(k_pipe_iter_g<JAC>));
             npend = false;
-        } else if (jac) {
-            go(g_tune.upd_preload ? k_pipe_iter<true, true> : k_pipe_iter<true, false>);
         } else {
-            go(g_tune.upd_preload ? k_pipe_iter<false, true> : k_pipe_iter<false, false>);
+            WITH_JAC(jac, go(g_tune.upd_preload ? k_pipe_iter<JAC, true> : k_pipe_iter<JAC, false>));
         }
-        if (hipGetLastError() != hipSuccess) { rc = fail(KLE_ERR_DEVICE, "k_pipe_iter launch failed"); break; }
-        if ((rc = c->toc("cg_update", &ev))) break;
+        KLE_HIP(hipGetLastError());
+        KLE_TRY(c->toc("cg_update", &ev));
         par ^= 1;
         pending = true;
-        if (fuse) {
-            // one rank: the next launch's prologue reduces these partials
-            if ((rc = product(c->d_istate))) break;
-        } else if (side && c->nranks > 1) {
+        KLE_TRY(product(c->d_istate));
+        // (one rank: the next launch's prologue reduces these partials)
+        if (!fuse && side && c->nranks > 1) {
             // the partials' allreduce on the comm stream behind the halo, beside
             // the SpMV; the overlapped SpMV already makes the comm stream wait
             // for the update (ev_x_ready), so no event of its own: each event
@@ -1620,47 +1623,33 @@ static int solve_pipecg(kle_ksp *k, kle_vec *b, kle_vec *x, bool cont)
             // (profiles/r02/sync_cost_eighth.jsonl)
             // (a split product's reverse halo went first on the comm stream:
             // the wait for the allreduce covers the received sums too)
-            if ((rc = product(c->d_istate))) break;
-            if ((rc = allreduce_sum(c, pp[par], 3 * G, c->comm_stream))) break;
-            if (hipEventRecord(ev_red, c->comm_stream) != hipSuccess ||
-                hipStreamWaitEvent(c->stream, ev_red, 0) != hipSuccess) {
-                rc = fail(KLE_ERR_DEVICE, "event record/wait failed");
-                break;
-            }
-        } else {
+            KLE_TRY(allreduce_sum(c, pp[par], 3 * G, c->comm_stream));
+            KLE_HIP(hipEventRecord(ev_red.e, c->comm_stream));
+            KLE_HIP(hipStreamWaitEvent(c->stream, ev_red.e, 0));
+        } else if (!fuse) {
             // no overlap possible on this rank (or a one-rank RCCL
             // communicator): same collective order as the overlapping ranks
             // (halo, then allreduce), all on one stream
-            if ((rc = product(c->d_istate))) break;
-            if (gfuse && gdist && k->A->halo_overlap &&
-                hipStreamWaitEvent(c->stream, c->ev_halo_done, 0) != hipSuccess) {  // (the received sums)
-                rc = fail(KLE_ERR_DEVICE, "event wait failed");
-                break;
-            }
-            if ((rc = allreduce_sum(c, pp[par], 3 * G, c->stream))) break;
+            if (gfuse && gdist && k->A->halo_overlap)
+                KLE_HIP(hipStreamWaitEvent(c->stream, c->ev_halo_done, 0));  // (the received sums)
+            KLE_TRY(allreduce_sum(c, pp[par], 3 * G, c->stream));
         }
         if (!k->fixed && ((it + 1) % k->check_every == 0)) {
-            if ((rc = poll_state(k))) break;
+            KLE_TRY(poll_state(k));
             if (c->h_istate[I_REASON] != 0) break;
         }
     }
-    if (!rc && pending) {
+    if (pending) {
         hipLaunchKernelGGL(k_cg_flush, dim3(1), dim3(KB), 0, c->stream, pp[par], pp[par] + G, G, pp[par] + 2 * G, G,
                            c->d_scal, c->d_istate, par, k->atol);
-        if (hipGetLastError() != hipSuccess) rc = fail(KLE_ERR_DEVICE, "k_cg_flush launch failed");
+        KLE_HIP(hipGetLastError());
     }
     // (n complete when the call returns: a continuation starts with the plain
     // update, and nothing may clobber the bricks' sums in between)
-    if (!rc && npend) rc = brick_gather_rest(k->A, k->m, k->nv, c->d_istate, 1);
+    if (npend) KLE_TRY(brick_gather_rest(k->A, k->m, k->nv, c->d_istate, 1));
     k->pipe_par = par;
-    hipEventDestroy(ev_red);
-    if (rc) return rc;
-    KLE_TRY(poll_state(k));
-    k->its = c->h_istate[I_ITS];
-    k->reason = c->h_istate[I_REASON];
-    if (k->reason == 0) k->reason = k->fixed ? KLE_CONVERGED_ITS : KLE_DIVERGED_ITS;
-    k->rnorm = std::sqrt(c->h_scal[S_RR]);
-    return 0;
+    ev_red.reset();  // (its last use was in the loop)
+    return solve_end(k);
 }
 
 // ------------------------------------------------------------------ GMRES

@@ -268,6 +268,18 @@ class Context:
 
 
 _CTX = None
+# environment variables that set one tuning key each when the context is made,
+# in this order; KLE_TUNING (any keys, as JSON) is applied after them
+_ENV_TUNING = {
+    "KLE_SPMV_WAVES": "spmv_waves",
+    "KLE_SPMV_SYM": "spmv_sym",
+    "KLE_SPMV_SYM_MIN_ROWS": "spmv_sym_min_rows",
+    "KLE_SPMV_DICT_MIN_ROWS": "spmv_dict_min_rows",
+    "KLE_SPMV_SYM_TILE64": "spmv_sym_tile64",
+    "KLE_SPMV_SYM_BRICK": "spmv_sym_brick",
+    "KLE_KSP_REFINE": "ksp_refine",
+    "KLE_SPMV_GSYM_BRICK": "spmv_gsym_brick",
+}
 
 
 def get_ctx():
@@ -277,22 +289,9 @@ def get_ctx():
             set_row_padding(int(os.environ["KLE_NB_PAD"]))
         if os.environ.get("KLE_NB_LAYOUT"):
             set_value_layout(int(os.environ["KLE_NB_LAYOUT"]))
-        if os.environ.get("KLE_SPMV_WAVES"):
-            set_tuning("spmv_waves", int(os.environ["KLE_SPMV_WAVES"]))
-        if os.environ.get("KLE_SPMV_SYM"):
-            set_tuning("spmv_sym", int(os.environ["KLE_SPMV_SYM"]))
-        if os.environ.get("KLE_SPMV_SYM_MIN_ROWS"):
-            set_tuning("spmv_sym_min_rows", int(os.environ["KLE_SPMV_SYM_MIN_ROWS"]))
-        if os.environ.get("KLE_SPMV_DICT_MIN_ROWS"):
-            set_tuning("spmv_dict_min_rows", int(os.environ["KLE_SPMV_DICT_MIN_ROWS"]))
-        if os.environ.get("KLE_SPMV_SYM_TILE64"):
-            set_tuning("spmv_sym_tile64", int(os.environ["KLE_SPMV_SYM_TILE64"]))
-        if os.environ.get("KLE_SPMV_SYM_BRICK"):
-            set_tuning("spmv_sym_brick", int(os.environ["KLE_SPMV_SYM_BRICK"]))
-        if os.environ.get("KLE_KSP_REFINE"):
-            set_tuning("ksp_refine", int(os.environ["KLE_KSP_REFINE"]))
-        if os.environ.get("KLE_SPMV_GSYM_BRICK"):
-            set_tuning("spmv_gsym_brick", int(os.environ["KLE_SPMV_GSYM_BRICK"]))
+        for var, key in _ENV_TUNING.items():
+            if os.environ.get(var):
+                set_tuning(key, int(os.environ[var]))
         if os.environ.get("KLE_TUNING"):  # any knobs, as JSON: KLE_TUNING='{"spmv_gather_wps": 2}'
             import json
             for k, v in json.loads(os.environ["KLE_TUNING"]).items():
@@ -314,8 +313,9 @@ def set_value_layout(layout):
 
 
 def set_tuning(key, value):
-    """libkle performance knob (kle_set_tuning): "spmv_waves"; every setting
-    gives correct results."""
+    """Set one libkle tuning key (kle_set_tuning); include/kle.h lists the
+    keys, their values and the few that are not pure performance knobs.
+    An unknown key or a refused value raises Error."""
     call("kle_set_tuning", key.encode(), int(value))
 
 
