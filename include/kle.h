@@ -524,13 +524,41 @@ int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **o
  * kle_ksp_set_operators with cg (classic and single reduction: the generic
  * paths), pipecg or gmres and PC none or jacobi.  Calls that need stored
  * values, and kle_mat_copy_dirichlet_rows, return KLE_ERR_SUP.
- * KLE_ERR_SUP also for which 2 (Rw), no-slip meshes, a mesh whose nranks is
+ * KLE_ERR_SUP also for which 2 (Rw: kle_mat_create_rw_sumfac), no-slip meshes, a mesh whose nranks is
  * not the context's and any mesh with nranks > 1; KLE_ERR_ARG for any other
  * which.  Every table index is checked on the host before upload
  * (connectivity inside the mesh, incidence consistent with it and ascending,
  * E ngl^dim and dim N below 2^31): a bad table is an error code, never a
  * launch. */
 int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* Sum-factorised element-wise Rw [dim N x dim_w N] (dim_w = 1 in 2-D, 3 in
+ * 3-D) of any one-rank mesh, box or unstructured: the Rw of kle_assemble_kle
+ * with no assembled values and no element matrix,
+ *     (Rw_e w)_l^a =  sum_{q in full} c_q N_l(q) (curl w)_a(q)
+ *                   + a_w sum_{q in red} c_q sum_b d_b N_l(q) eps_{acb} w_c(q)
+ * (2-D: y_0 = sum c N_l d_y w - a_w sum c d_y N_l w, y_1 = -sum c N_l d_x w +
+ * a_w sum c d_x N_l w).  k_sumfac_rw has the batching, LDS tiles, tables and
+ * geometry of k_sumfac_elem.  Full rule: forward passes with h / dh, inv J,
+ * c curl w, value passes back (h transposed).  Reduced rule: forward value
+ * passes, the flux c (a_w w_c) placed by eps, inv J^T, the transposed
+ * derivative passes; its sum is added to the full rule's.  No entry of w is
+ * dropped.  k_sumfac_gather_rw sums a free row's incidence entries in
+ * ascending element order; a Dirichlet row is +0.0 and reads nothing, as the
+ * assembled Rw has no entry there.  No atomics: the same input gives the same
+ * bits.
+ * K, Krhs and Rw of one mesh share the two geometry tables: the mesh hands out
+ * one reference-counted set, freed with its last holder (operators may be
+ * destroyed in any order, the mesh before them).
+ * The result is a kle_mat of format 2 ("elem") with the call surface of
+ * kle_mat_create_kle_element's Rw: kle_mat_mult, kle_mat_mult_add, the size
+ * and ownership getters, kle_mat_get_info (nz_used 0), kle_mat_spmv_bytes,
+ * kle_mat_spmv_kernel ("k_sumfac_rw<D>+k_sumfac_gather_rw<D>") and
+ * kle_mat_time_local_spmv.  KLE_ERR_SUP: kle_mat_get_diagonal,
+ * kle_mat_copy_dirichlet_rows, every call that needs stored values, no-slip
+ * meshes, a mesh whose nranks is not the context's and any mesh with
+ * nranks > 1.  kle_ksp_set_operators refuses the non-square 2-D Rw before any
+ * launch.  Every table index is checked on the host before upload. */
+int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out);
 /* Element-wise no-slip operator of a uniform box mesh: the matrices of
  * kle_assemble_ns (MatNS.buildNS, mat_ns.py:47-145) with no stored values.
  * which: 0 K, 1 Krhs, 2 Rw, 3 Kfs, 4 Krhsfs, 5 Rwfs, 6 K + Kfs (the operator
@@ -605,6 +633,26 @@ int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **ou
  * for unstructured meshes and a mesh whose nranks is not the context's,
  * KLE_ERR_ARG for a bad which. */
 int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* The same collocation operators (which 0 Curl, 1 SrT, 2 DivSrT) with every
+ * element's own geometry, on any one-rank mesh, box or unstructured, 2-D or
+ * 3-D, ngl 2..8, free-slip or no-slip:
+ *     y = Winv sum_e S_e^T M_e S_e^c x.
+ * k_colloc_elem reads c_l and inv J of its own element from the nodal table
+ * [E][nn][1 + dim^2] that the assembly's geometry kernel fills at the operator
+ * points over all local elements (the table kle_assemble_operators builds).
+ * The gather runs over a CSR incidence list (any valence, ascending element),
+ * then times winv[node]; winv = 1 / sum_e c_{e,l(n)} in ascending incidence
+ * order, the assembled operators' weights bit for bit.  The three operators
+ * of a mesh share the nodal table, and at ngl > 3, where the full rule's
+ * points and weights are the operator points' bit for bit (checked on the
+ * host), it is the full-rule table of kle_mat_create_kle_sumfac and
+ * kle_mat_create_rw_sumfac.
+ * Call surface and refusals as kle_mat_create_operator_element
+ * (kle_mat_spmv_kernel: "k_colloc_elem<D,Op,geo>+k_colloc_gather_csr<RW>").
+ * KLE_ERR_SUP for nranks > 1 and a mesh whose nranks is not the context's,
+ * KLE_ERR_ARG for a bad which; connectivity and incidence are checked on the
+ * host before upload. */
+int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Dense collocation element matrices of local element e as the assembly forms
  * them, before the nodal weight (parity tests, the creation check above):
  * Curl_e [dim_w n][dim n], SrT_e [dim_s n][dim n], DivSrT_e [dim n][dim_s n]

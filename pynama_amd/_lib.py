@@ -130,6 +130,8 @@ _SIGS = {
     "kle_mat_create_ns_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_operator_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_kle_sumfac": [vp, vp, C.c_int, pvp],
+    "kle_mat_create_rw_sumfac": [vp, vp, pvp],
+    "kle_mat_create_operator_sumfac": [vp, vp, C.c_int, pvp],
     "kle_element_ops": [vp, vp, C.c_int64, f64p, f64p, f64p, f64p],
     "kle_mat_copy_dirichlet_rows": [vp, vp, vp],
     "kle_mat_create_aij": [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, pvp],

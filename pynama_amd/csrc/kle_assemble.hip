@@ -1368,21 +1368,77 @@ static int element_matrices(kle_ctx *ctx, const kle_mesh *m, double **dKe, doubl
     return 0;
 }
 
-// The Gauss-point geometry of every local element at the full and the reduced
-// rule, [e][q][1 + dim^2] each (c_q = w_q det J, inv J): the tables the element
-// kernels above read, from the mesh's own corners, handed to the caller (who
-// frees both) for the sum-factorised operator (kle_sumfac.hip).
-int element_geometry(kle_ctx *ctx, const kle_mesh *m, double **gF, double **gR, int *npF, int *npR)
+// The point geometry of every local element (GeoSet, kle_internal.hpp): the
+// tables the element kernels above and the operator gathers below read, from
+// the mesh's own corners, for the matrix-free operators (kle_sumfac.hip,
+// kle_colloc.hip).  The mesh keeps a weak reference, so the operators of one
+// mesh share one set and the last of them to go frees it; corners never
+// change after mesh creation, so a table once filled stays valid.
+GeoSet::~GeoSet()
 {
-    *gF = *gR = nullptr;
-    ElemSetup S;
-    KLE_TRY(element_setup(ctx, m, S));
-    KLE_HIP(hipStreamSynchronize(ctx->stream));
-    *gF = S.gF;
-    *gR = S.gR;
-    S.gF = S.gR = nullptr;
-    *npF = S.T.F.np1;
-    *npR = S.T.R.np1;
+    if (O && O != F) (void)hipFree(O);
+    if (F) (void)hipFree(F);
+    if (R) (void)hipFree(R);
+}
+
+int mesh_geometry(kle_ctx *ctx, kle_mesh *m, bool kle, bool ops, std::shared_ptr<GeoSet> *out)
+{
+    std::shared_ptr<GeoSet> G = m->geo_set.lock();
+    if (!G || G->ctx != ctx) {
+        G = std::make_shared<GeoSet>();
+        G->ctx = ctx;
+        m->geo_set = G;
+    }
+    const int dim = m->dim, nc = 1 << dim, G1 = 1 + dim * dim;
+    PointSet1D full, red, op;
+    element_sets(m->ngl, full, red, op);
+    // the operator points are the full rule's: both tables are one
+    const bool same = full.x.size() == op.x.size() &&
+                      memcmp(full.x.data(), op.x.data(), sizeof(double) * op.x.size()) == 0 &&
+                      memcmp(full.w.data(), op.w.data(), sizeof(double) * op.w.size()) == 0;
+    const bool wantF = (kle || (ops && same)) && !G->F, wantR = kle && !G->R, wantO = ops && !same && !G->O;
+    if (wantF || wantR || wantO) {
+        KLE_HIP(hipSetDevice(ctx->device));
+        const int64_t nel = m->elem_end - m->elem_begin;
+        DevTables T;
+        KLE_TRY(upload_tables(ctx, m->ngl, T));
+        std::vector<double> corners(std::max<int64_t>(nel * nc * dim, 1));
+        KLE_TRY(kle_mesh_get_corners(m, corners.data()));
+        double *dX = nullptr;
+        KLE_HIP(hipMalloc(&dX, sizeof(double) * corners.size()));
+        hipError_t he = hipMemcpyAsync(dX, corners.data(), sizeof(double) * corners.size(), hipMemcpyHostToDevice,
+                                       ctx->stream);
+        int rc = 0;
+        auto fill = [&](const Tables1D &t, double **dst, int *np) {
+            if (rc || he != hipSuccess) return;
+            const int64_t n = nel * (dim == 2 ? t.np1 * t.np1 : t.np1 * t.np1 * t.np1);
+            double *g = nullptr;
+            if (hipMalloc(&g, sizeof(double) * std::max<int64_t>(n * G1, 1)) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = fail(KLE_ERR_MEM, "out of device memory for the element geometry");
+                return;
+            }
+            if (n > 0) {
+                if (dim == 2) hipLaunchKernelGGL(k_geometry<2>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, nel, m->ngl, t, dX, g);
+                else hipLaunchKernelGGL(k_geometry<3>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, nel, m->ngl, t, dX, g);
+                he = hipGetLastError();
+            }
+            *dst = g;  // (owned by the set from here on)
+            *np = t.np1;
+        };
+        if (wantF) fill(T.F, &G->F, &G->npF);
+        if (wantR) fill(T.R, &G->R, &G->npR);
+        if (wantO) fill(T.O, &G->O, &G->npO);
+        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(dX);
+        if (rc) return rc;
+        if (he != hipSuccess) return fail(KLE_ERR_DEVICE, "element geometry: %s", hipGetErrorString(he));
+    }
+    if (ops && same) {
+        G->O = G->F;
+        G->npO = G->npF;
+    }
+    *out = G;
     return 0;
 }
 

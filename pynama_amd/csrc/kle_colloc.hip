@@ -1,5 +1,7 @@
-// kle_colloc.hip -- element-wise Curl, SrT and DivSrT of a uniform box mesh
-// (kle_mat kind 2 with colloc set): no assembled values.
+// kle_colloc.hip -- element-wise Curl, SrT and DivSrT (kle_mat kind 2 with
+// colloc set): no assembled values.  Of a uniform box mesh with one element's
+// geometry (kle_mat_create_operator_element), of any one-rank mesh with every
+// element's own (kle_mat_create_operator_sumfac, at the end of this header).
 //
 // The operators (kle_assemble.hip "operators") are collocation operators on
 // the GLL nodes: row (l, a) of an element matrix M_e holds entries only at the
@@ -38,10 +40,26 @@
 // is computed whole although only its top plane is gathered.  geo is that of
 // global element 0 on every rank: the owned rows are the one-rank product's
 // bit for bit.
+//
+// Per-element geometry (any one-rank mesh, box or unstructured):
+//
+//     y = Winv  sum over elements e of  S_e^T  M_e  S_e^c x,
+//
+//   k_colloc_elem<DIM, OP, true>  the same kernel reading c_l and inv J of its
+//       own element from the nodal table [E][nn][1 + dim^2] that k_geometry
+//       fills at the operator points (the one kle_assemble_operators builds
+//       for k_ops_gather_u; the mesh's shared set, mesh_geometry).
+//   k_colloc_gather_csr<RW>  one thread per node: its incidence entries of ws
+//       through a CSR list (inc_ptr, inc_idx = e nn + l, ascending e: any
+//       valence), times winv[node].
+//   k_colloc_weights         once at creation: winv = 1 / sum of the incident
+//       c_{e,l}, in incidence order (k_ops_weights_u's sum, so the weights
+//       are the assembled operators' bit for bit).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
+#include "kle_basis.hpp"
 #include "kle_internal.hpp"
 
 namespace kle {
@@ -60,6 +78,12 @@ struct CollocOp {
     double *d_ws = nullptr;     // [E][nn][rw] element results
     int32_t *d_conn = nullptr;  // [E][nn] element -> ext-local node, tensor order
     int32_t *d_inc = nullptr;   // [N][maxinc] owned node -> e * nn + l, ascending e, -1 padded
+    // per-element geometry (kle_mat_create_operator_sumfac): d_geo is the nodal
+    // table [E][nn][1 + dim^2] of the mesh's set, d_inc a CSR list [ninc] behind d_incp
+    bool per_elem = false;
+    std::shared_ptr<GeoSet> geo;
+    int32_t *d_incp = nullptr;  // [N + 1]
+    int64_t ninc = 0;
 };
 
 // OP 0 Curl [dim_w x dim], 1 SrT [dim_s x dim], 2 DivSrT [dim x dim_s]
@@ -98,7 +122,8 @@ __host__ __device__ constexpr double colloc_coef(int a, int b, int d)
     }
 }
 
-template <int DIM, int OP>
+// PE: geo holds every element's table, [E][nn][G1], instead of the first element's
+template <int DIM, int OP, bool PE = false>
 __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t eb,
                                                      int64_t E,
                                                      const double *__restrict__ dh, const double *__restrict__ geo,
@@ -150,7 +175,7 @@ __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, i
 #pragma unroll
                 for (int d = 0; d < DIM; ++d) h[b][d] += dm[d] * sx[b * SC + o[d]];
         }
-        const double *g = geo + l * G1;
+        const double *g = PE ? geo + (t0 + t) * G1 : geo + l * G1;
         const double c = g[0];
         double Ji[DIM][DIM];
 #pragma unroll
@@ -209,11 +234,60 @@ __global__ __launch_bounds__(256) void k_colloc_gather(int64_t N, int maxinc, co
     for (int a = 0; a < RW; ++a) y[node * RW + a] = s[a] * wi;
 }
 
+template <int RW>
+__global__ __launch_bounds__(256) void k_colloc_gather_csr(int64_t N, const int32_t *__restrict__ incp,
+                                                           const int32_t *__restrict__ inc,
+                                                           const double *__restrict__ winv,
+                                                           const double *__restrict__ ws, double *__restrict__ y,
+                                                           const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (node >= N) return;
+    double s[RW];
+#pragma unroll
+    for (int a = 0; a < RW; ++a) s[a] = 0.0;
+    const int j1 = incp[node + 1];
+    for (int j = incp[node]; j < j1; ++j) {
+        const double *w = ws + (int64_t)inc[j] * RW;
+#pragma unroll
+        for (int a = 0; a < RW; ++a) s[a] += w[a];
+    }
+    const double wi = winv[node];
+#pragma unroll
+    for (int a = 0; a < RW; ++a) y[node * RW + a] = s[a] * wi;
+}
+
+// winv of the per-element geometry: k_ops_weights_u's sum over the CSR list
+__global__ __launch_bounds__(256) void k_colloc_weights(int64_t N, int G1, const int32_t *__restrict__ incp,
+                                                        const int32_t *__restrict__ inc,
+                                                        const double *__restrict__ geo, double *__restrict__ winv)
+{
+    const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (node >= N) return;
+    double W = 0.0;
+    const int j1 = incp[node + 1];
+    for (int j = incp[node]; j < j1; ++j) W += geo[(int64_t)inc[j] * G1];
+    winv[node] = 1.0 / W;
+}
+
 // the element kernel over elements [e0, e1) (x: the ghosted allocation), or with e0 < 0 the gather
 template <int DIM, int OP>
 static void launch_colloc(const CollocOp *P, hipStream_t st, int64_t e0, int64_t e1, const double *x, double *y,
                           const int *istate)
 {
+    if (P->per_elem) {  // one rank: every element, then the CSR gather
+        if (e0 >= 0) {
+            const unsigned ge = (unsigned)((e1 - e0 + P->neb - 1) / P->neb);
+            hipLaunchKernelGGL((k_colloc_elem<DIM, OP, true>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,
+                               P->sz, P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate);
+            return;
+        }
+        const unsigned gn = (unsigned)((P->N + 255) / 256);
+        hipLaunchKernelGGL((k_colloc_gather_csr<colloc_rw(DIM, OP)>), dim3(gn), dim3(256), 0, st, P->N, P->d_incp,
+                           P->d_inc, P->d_winv, P->d_ws, y, istate);
+        return;
+    }
     if (e0 >= 0) {
         const unsigned ge = (unsigned)((e1 - e0 + P->neb - 1) / P->neb);
         hipLaunchKernelGGL((k_colloc_elem<DIM, OP>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz,
@@ -244,6 +318,10 @@ int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, boo
         KLE_HIP(hipGetLastError());
         return 0;
     };
+    if (P->per_elem) {
+        KLE_TRY(launch(0, P->E));
+        return launch(-1, -1);
+    }
     // (the ghost layer whole: a workgroup takes whole elements)
     KLE_TRY(elem_ranges(A, x, local, [&](int64_t e0, int64_t e1, bool) -> int { return launch(e0, e1); }));
     return launch(-1, -1);
@@ -254,7 +332,8 @@ void colloc_drop(kle_mat *A)
     CollocOp *P = A->colloc;
     if (!P) return;
     (void)hipFree(P->d_dh);
-    (void)hipFree(P->d_geo);
+    if (!P->per_elem) (void)hipFree(P->d_geo);  // (else the mesh's set: it goes with its last holder)
+    (void)hipFree(P->d_incp);
     (void)hipFree(P->d_winv);
     (void)hipFree(P->d_ws);
     (void)hipFree(P->d_conn);
@@ -271,6 +350,10 @@ double colloc_spmv_bytes(const kle_mat *A)
 {
     const CollocOp *P = A->colloc;
     if (!P) return 0.0;
+    if (P->per_elem)  // every element's geometry, the CSR list instead of the padded table
+        return 4.0 * P->E * P->nn + 8.0 * A->n_local + 8.0 * P->ngl * P->ngl +
+               8.0 * P->E * P->nn * (1 + P->dim * P->dim) + 2.0 * 8.0 * P->E * P->nn * P->rw + 4.0 * (P->N + 1) +
+               4.0 * P->ninc + 8.0 * P->N + 8.0 * A->m_local;
     return 4.0 * P->E * P->nn + 8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * P->ngl * P->ngl + 8.0 * P->nn * (1 + P->dim * P->dim) +
            2.0 * 8.0 * P->E * P->nn * P->rw + 4.0 * P->N * P->maxinc + 8.0 * P->N + 8.0 * A->m_local;
 }
@@ -280,6 +363,9 @@ std::string colloc_kernel_name(const kle_mat *A)
     const CollocOp *P = A->colloc;
     if (!P) return "?";
     const char *ops[3] = {"Curl", "SrT", "DivSrT"};
+    if (P->per_elem)
+        return "k_colloc_elem<" + std::to_string(P->dim) + "," + ops[P->which] + ",geo>+k_colloc_gather_csr<" +
+               std::to_string(P->rw) + ">";
     return "k_colloc_elem<" + std::to_string(P->dim) + "," + ops[P->which] + ">+k_colloc_gather<" +
            std::to_string(P->rw) + ">";
 }
@@ -442,6 +528,117 @@ extern "C" int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int wh
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * rw);
+    if (rc) {
+        kle_mat_destroy(A);
+        return rc;
+    }
+    *out = A;
+    return 0;
+}
+
+// The same operators with every element's own geometry: any one-rank mesh.
+extern "C" int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which >= 0 && which <= 2, "which must be 0 (Curl), 1 (SrT) or 2 (DivSrT)");
+    if (m->nranks != ctx->nranks)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
+                    m->nranks, ctx->nranks);
+    if (m->nranks > 1) return fail(KLE_ERR_SUP, "sum-factorised operator: one rank only");
+    const int dim = m->dim, ngl = m->ngl, nn = m->nn(), G1 = 1 + dim * dim;
+    KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "sum-factorised operator: dim 2 or 3, ngl 2..8");
+    const int rw = colloc_rw(dim, which), cw = colloc_cw(dim, which);
+    ElemLayout L;
+    L.N = L.next = m->node_end - m->node_begin;
+    L.E = L.eint1 = m->n_local_elems();
+    const int64_t E = L.E, N = L.N;
+    KLE_ARG(E >= 1 && N >= 1 && m->node_begin == 0 && m->ext_begin == 0 && m->ext_end == N && N == m->N,
+            "unexpected one-rank layout");
+    if (E * nn >= INT32_MAX || N * std::max(rw, cw) >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
+
+    // connectivity and CSR incidence list (host), validated before upload
+    std::vector<int64_t> conn64((size_t)E * nn);
+    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
+    std::vector<int32_t> conn((size_t)E * nn), incp((size_t)N + 1, 0), inc((size_t)E * nn, -1);
+    for (int64_t k = 0; k < E * nn; ++k) {
+        if (conn64[k] < 0 || conn64[k] >= N)
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld outside the mesh", (long long)k);
+        conn[k] = (int32_t)conn64[k];
+        ++incp[conn[k] + 1];
+    }
+    for (int64_t i = 0; i < N; ++i) incp[i + 1] += incp[i];
+    {
+        std::vector<int32_t> fill(incp.begin(), incp.end() - 1);
+        for (int64_t k = 0; k < E * nn; ++k) inc[fill[conn[k]]++] = (int32_t)k;  // k = e * nn + l, ascending e
+    }
+    KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, std::max(rw, cw)));
+    for (int64_t i = 0; i < N; ++i)
+        if (incp[i + 1] == incp[i])
+            return fail(KLE_ERR_STATE, "sum-factorised operator: node %lld lies in no element", (long long)i);
+
+    const int neb = std::max(1, 256 / nn);
+    const int sy = ngl | 1, sz = dim == 3 ? (ngl * sy) | 1 : 0, se = ngl * (dim == 3 ? sz : sy) | (neb > 1 ? 1 : 0);
+    if ((int64_t)neb * se > (dim == 3 ? CL_SC3 : CL_SC2))
+        return fail(KLE_ERR_STATE, "collocation operator: %d elements of stride %d exceed the LDS tile", neb, se);
+
+    // the derivative table at the operator points: the assembly's (T.O.dh)
+    PointSet1D full, red, op;
+    element_sets(ngl, full, red, op);
+    if ((int)op.x.size() != ngl || (int)op.dh.size() != ngl * ngl)
+        return fail(KLE_ERR_STATE, "operator points are not the element's nodes");
+
+    KLE_HIP(hipSetDevice(ctx->device));
+    kle_mat *A = new kle_mat;
+    CollocOp *P = new CollocOp;
+    A->ctx = ctx;
+    A->colloc = P;
+    elem_mat_fields(A, m, L, rw, cw);
+    P->which = which;
+    P->dim = dim;
+    P->cw = cw;
+    P->rw = rw;
+    P->ngl = ngl;
+    P->nn = nn;
+    P->maxinc = 0;
+    P->neb = neb;
+    P->sy = sy;
+    P->sz = sz;
+    P->se = se;
+    P->E = E;
+    P->N = N;
+    P->per_elem = true;
+    P->ninc = E * nn;
+    auto up = [&](auto **dp, const void *src, size_t bytes) {
+        if (hipMalloc(dp, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *dp = nullptr;
+            return fail(KLE_ERR_MEM, "out of device memory for the sum-factorised operator");
+        }
+        return src ? h2d(*dp, src, bytes) : 0;
+    };
+    int rc = mesh_geometry(ctx, m, false, true, &P->geo);
+    if (!rc && P->geo->npO != ngl) rc = fail(KLE_ERR_STATE, "sum-factorised operator: the nodal geometry does not match the element");
+    if (!rc) P->d_geo = P->geo->O;
+    if (!rc) rc = up(&P->d_dh, op.dh.data(), sizeof(double) * op.dh.size());
+    if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
+    if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
+    if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc) rc = up(&P->d_winv, nullptr, sizeof(double) * (size_t)N);
+    if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * rw);
+    if (!rc) {
+        hipStream_t st = ctx->stream;
+        hipLaunchKernelGGL(k_colloc_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, G1, P->d_incp,
+                           P->d_inc, P->d_geo, P->d_winv);
+        hipError_t he = hipGetLastError();
+        std::vector<double> winv((size_t)N);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he == hipSuccess) he = hipMemcpy(winv.data(), P->d_winv, sizeof(double) * winv.size(), hipMemcpyDeviceToHost);
+        if (he != hipSuccess) rc = fail(KLE_ERR_DEVICE, "sum-factorised operator: weights: %s", hipGetErrorString(he));
+        for (int64_t g = 0; g < N && !rc; ++g)
+            if (!std::isfinite(winv[g]))
+                rc = fail(KLE_ERR_STATE, "sum-factorised operator: node %lld has no finite nodal weight", (long long)g);
+    }
     if (rc) {
         kle_mat_destroy(A);
         return rc;

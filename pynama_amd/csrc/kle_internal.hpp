@@ -73,6 +73,7 @@ struct HaloPlan {
 };
 using PlanPtr = std::shared_ptr<HaloPlan>;
 struct IpcState;  // kle_ipc.hip: IPC-mapped mailboxes (KLE_TRANSPORT=ipc)
+struct GeoSet;    // kle_assemble.hip: a mesh's point geometry tables, shared by its matrix-free operators
 
 // Device scalar slots used by the Krylov kernels.
 enum Scal {
@@ -145,6 +146,9 @@ struct kle_mesh {
     int64_t elem_layer = 1;  // elements per layer of the partition axis
     std::vector<uint8_t> dir;  // Dirichlet flag per ext node (index - ext_begin)
     bool dir_set = false;
+    // the geometry tables the sum-factorised operators of this mesh share
+    // (mesh_geometry); the operators hold them, the mesh only finds them
+    std::weak_ptr<kle::GeoSet> geo_set;
     // no-slip: class of every velocity DoF of the ext range (DOF_FREE /
     // DOF_TANG / DOF_NORMAL, mat_ns.py:58-70); empty for free-slip meshes
     std::vector<uint8_t> dof_cls;
@@ -460,8 +464,20 @@ int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, boo
 void colloc_drop(kle_mat *A);
 double colloc_spmv_bytes(const kle_mat *A);
 std::string colloc_kernel_name(const kle_mat *A);
-// sum-factorised K and Krhs (kle_sumfac.hip; kle_mat kind 2 with sumfac set)
-int element_geometry(kle_ctx *ctx, const kle_mesh *m, double **gF, double **gR, int *npF, int *npR);  // kle_assemble.hip
+// Point geometry [e][q][1 + dim^2] (c_q, inv J) of every local element, from
+// the mesh's own corners (k_geometry): F the full rule, R the reduced rule, O
+// the operator points (the element's nodes).  One set per mesh and context,
+// held by the operators that read it; where the full rule's 1-D points and
+// weights are the operator points' bit for bit (ngl > 3) O is F.
+struct GeoSet {
+    kle_ctx *ctx = nullptr;
+    double *F = nullptr, *R = nullptr, *O = nullptr;
+    int npF = 0, npR = 0, npO = 0;
+    ~GeoSet();
+};
+// the mesh's set with F and R (kle) and / or O (ops) filled  (kle_assemble.hip)
+int mesh_geometry(kle_ctx *ctx, kle_mesh *m, bool kle, bool ops, std::shared_ptr<GeoSet> *out);
+// sum-factorised K, Krhs and Rw (kle_sumfac.hip; kle_mat kind 2 with sumfac set)
 int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
 int sumfac_diagonal(const kle_mat *A, kle_vec *d);
 void sumfac_drop(kle_mat *A);

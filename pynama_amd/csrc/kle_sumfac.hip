@@ -1,4 +1,4 @@
-// kle_sumfac.hip -- sum-factorised element-wise K and Krhs on any one-rank
+// kle_sumfac.hip -- sum-factorised element-wise K, Krhs and Rw on any one-rank
 // mesh, box or unstructured (kle_mat kind 2 with sumfac set): no assembled
 // values and no element matrix.
 //
@@ -44,9 +44,25 @@
 //       per (element, node), gathered like the product; 1 on Dirichlet rows, 0
 //       on the free rows of Krhs.
 //
+//   k_sumfac_rw<DIM>      Rw applied to a vorticity vector w (dim_w = 3
+//       components in 3-D, 1 in 2-D), the same batching, tiles, tables and
+//       geometry as k_sumfac_elem:
+//         (Rw_e w)_l^a =  sum_{q in full} c_q N_l(q) (curl w)_a(q)
+//                       + a_w sum_{q in red} c_q sum_b d_b N_l(q) eps_{acb} w_c(q)
+//       (2-D: y_0 = sum c N_l d_y w - a_w sum c d_y N_l w, y_1 the same in x
+//       with the signs turned).  Full rule: the forward passes of
+//       k_sumfac_elem per component of w, inv J, c curl w, then value passes
+//       back (h transposed, no derivative table).  Reduced rule: forward value
+//       passes only, the flux c (a_w w_c) placed by eps, back with inv J^T and
+//       the transposed derivative passes of k_sumfac_elem.  No entry of w is
+//       dropped; ws[e][l][a] takes the sum.
+//   k_sumfac_gather_rw<DIM>  as k_sumfac_gather, but a Dirichlet row is +0.0
+//       and reads nothing (the assembled Rw has no entry there).
+//
 // c_q and inv J come from two tables [e][q][1 + dim^2], one per rule, that the
 // assembly's k_geometry fills from the mesh's own corners: the numbers the
-// assembled matrix was formed from.  No atomics, fixed order: the same input
+// assembled matrix was formed from; K, Krhs and Rw of one mesh share them
+// (mesh_geometry).  No atomics, fixed order: the same input
 // gives the same bits.  Both product kernels do nothing once the Krylov reason
 // word is set.  One rank only: the index-list halos of a graph partition are
 // not handled.
@@ -71,10 +87,11 @@ struct SumfacOp {
     int npF = 0, npR = 0;       // 1-D points of the full and the reduced rule
     int64_t E = 0, N = 0, ninc = 0;
     double *d_tab = nullptr;    // [4][8][8] h, dh of the full rule, h, dh of the reduced rule: [q][a], row length ngl
+    std::shared_ptr<GeoSet> geo;  // the mesh's geometry set: owns the two tables below
     double *d_geoF = nullptr;   // [E][npF^dim][1 + dim^2] c_q, inv J
     double *d_geoR = nullptr;   // [E][npR^dim][1 + dim^2]
     double *d_ws = nullptr;     // [E][nn][dim] element results
-    double *d_diag = nullptr;   // [N dim] the diagonal, formed at creation
+    double *d_diag = nullptr;   // [N dim] the diagonal, formed at creation (Rw: none)
     int32_t *d_conn = nullptr;  // [E][nn] element -> node, tensor order; -1 where the operator drops the entry
     int32_t *d_incp = nullptr;  // [N + 1] node -> its entries of d_inc
     int32_t *d_inc = nullptr;   // [E nn] e * nn + l, ascending e per node
@@ -340,6 +357,396 @@ __global__ __launch_bounds__(256) void k_sumfac_gather(int64_t N, const int32_t 
     y[i] = s;
 }
 
+// Rw_e w of a batch of whole elements: see the header.  The tiles, strides,
+// tables and site decoding are k_sumfac_elem's.
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
+                                                   const double *__restrict__ tab, const double *__restrict__ geoF,
+                                                   const double *__restrict__ geoR, const int32_t *__restrict__ conn,
+                                                   const double *__restrict__ x, double *__restrict__ ws,
+                                                   const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    constexpr int NIT = DIM == 3 ? 2 : 1;  // sites per thread: 512 at ngl 8 in 3-D
+    constexpr int DW = DIM == 3 ? 3 : 1;   // components of w
+    constexpr int G1 = 1 + DIM * DIM, SC = DIM == 3 ? SF_SC3 : SF_SC2;
+    __shared__ double sx[DW * SC];                  // w, per component
+    __shared__ double sA[2 * SC];                   // after the x pass: (h w, dh w); before the transposed x pass
+    __shared__ double sB[DIM * SC];                 // after the y pass (3-D); the point fluxes
+    __shared__ double sC[DIM == 3 ? 3 * SC : 1];    // after the transposed z pass (3-D); the reduced x pass (3-D)
+    __shared__ double sd[4 * SF_ST];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * neb;
+    const int nt = (int)min((int64_t)neb, E - e0) * nn;  // (element, site) pairs of this batch
+    const int64_t t0 = e0 * nn;
+    {
+        const int n2 = ngl * ngl;
+        for (int t = tid; t < 4 * n2; t += 256) {
+            const int tb = t / n2, r = t - tb * n2;
+            sd[tb * SF_ST + (r / ngl) * SF_SD + r % ngl] = tab[tb * 64 + r];
+        }
+    }
+    bool ok[NIT];
+    int base[NIT], si[NIT], sj[NIT], sk[NIT], sel[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int t = tid + it * 256;
+        ok[it] = t < nt;
+        const int el = t / nn, l = t - el * nn;
+        const int r = l / ngl;
+        si[it] = l % ngl;
+        sj[it] = DIM == 3 ? r % ngl : r;
+        sk[it] = DIM == 3 ? r / ngl : 0;
+        sel[it] = el;
+        base[it] = el * se + sk[it] * sz + sj[it] * sy + si[it];
+        if (ok[it]) {
+            const int64_t node = conn[t0 + t];  // (Rw drops no column)
+#pragma unroll
+            for (int b = 0; b < DW; ++b) sx[b * SC + base[it]] = x[node * DW + b];
+        }
+    }
+    double res[NIT][DIM];
+    // ================= full rule: c N_l curl w
+    {
+        const int P = ngl;
+        const double *th = sd, *tdh = th + SF_ST;
+        const int nq = DIM == 3 ? P * P * P : P * P;
+        double g[NIT][DW][DIM];  // [component][reference direction]
+        __syncthreads();         // w and the tables
+        // ---- forward: reference gradient of every component at the points
+#pragma unroll
+        for (int a = 0; a < DW; ++a) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int i = si[it], o = a * SC + base[it] - i;
+                double ah = 0.0, ad = 0.0;
+                for (int m = 0; m < ngl; ++m) {
+                    const double v = sx[o + m];
+                    ah += th[i * SF_SD + m] * v;
+                    ad += tdh[i * SF_SD + m] * v;
+                }
+                sA[base[it]] = ah;
+                sA[SC + base[it]] = ad;
+            }
+            __syncthreads();
+            if constexpr (DIM == 2) {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int j = sj[it], o = base[it] - j * sy;
+                    double g0 = 0.0, g1 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        g0 += th[j * SF_SD + m] * sA[SC + o + m * sy];
+                        g1 += tdh[j * SF_SD + m] * sA[o + m * sy];
+                    }
+                    g[it][a][0] = g0;
+                    g[it][a][1] = g1;
+                }
+            } else {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int j = sj[it], o = base[it] - j * sy;
+                    double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        const double ah = sA[o + m * sy], ad = sA[SC + o + m * sy];
+                        const double hj = th[j * SF_SD + m], dj = tdh[j * SF_SD + m];
+                        b0 += hj * ad;
+                        b1 += dj * ah;
+                        b2 += hj * ah;
+                    }
+                    sB[base[it]] = b0;
+                    sB[SC + base[it]] = b1;
+                    sB[2 * SC + base[it]] = b2;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+                    const int k = sk[it], o = base[it] - k * sz;
+                    double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        const double hk = th[k * SF_SD + m], dk = tdh[k * SF_SD + m];
+                        g0 += hk * sB[o + m * sz];
+                        g1 += hk * sB[SC + o + m * sz];
+                        g2 += dk * sB[2 * SC + o + m * sz];
+                    }
+                    g[it][a][0] = g0;
+                    g[it][a][1] = g1;
+                    g[it][a][2] = g2;
+                }
+            }
+        }
+        __syncthreads();  // the last component's reads of sA (2-D) and sB (3-D)
+        // ---- the point: physical gradient, c curl w into sB
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+            const int q = (sk[it] * P + sj[it]) * P + si[it];
+            const double *gp = geoF + ((e0 + sel[it]) * nq + q) * G1;
+            const double c = gp[0];
+            double Ji[DIM][DIM];
+#pragma unroll
+            for (int b = 0; b < DIM; ++b)
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) Ji[b][k] = gp[1 + b * DIM + k];
+            double G[DW][DIM];  // G[a][b] = d_b w_a
+#pragma unroll
+            for (int a = 0; a < DW; ++a)
+#pragma unroll
+                for (int b = 0; b < DIM; ++b) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < DIM; ++k) s += Ji[b][k] * g[it][a][k];
+                    G[a][b] = s;
+                }
+            if constexpr (DIM == 3) {
+                sB[base[it]] = c * (G[2][1] - G[1][2]);
+                sB[SC + base[it]] = c * (G[0][2] - G[2][0]);
+                sB[2 * SC + base[it]] = c * (G[1][0] - G[0][1]);
+            } else {
+                sB[base[it]] = c * G[0][1];
+                sB[SC + base[it]] = -(c * G[0][0]);
+            }
+        }
+        __syncthreads();
+        // ---- value passes back, every component: z, y, x with h read transposed, q ascending
+        if constexpr (DIM == 3) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                const int k = sk[it], o = base[it] - k * sz;
+                double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    const double hk = th[m * SF_SD + k];
+                    c0 += hk * sB[o + m * sz];
+                    c1 += hk * sB[SC + o + m * sz];
+                    c2 += hk * sB[2 * SC + o + m * sz];
+                }
+                sC[base[it]] = c0;
+                sC[SC + base[it]] = c1;
+                sC[2 * SC + base[it]] = c2;
+            }
+            __syncthreads();
+        }
+        {
+            const double *sY = DIM == 3 ? sC : sB;  // the y pass's input
+            double *sX = DIM == 3 ? sB : sA;        // ... and its output, the x pass's input
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int j = sj[it], o = base[it] - j * sy;
+                double d[DIM];
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) d[a] = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    const double hj = th[m * SF_SD + j];
+#pragma unroll
+                    for (int a = 0; a < DIM; ++a) d[a] += hj * sY[a * SC + o + m * sy];
+                }
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) sX[a * SC + base[it]] = d[a];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!ok[it]) continue;
+                const int i = si[it], o = base[it] - i;
+                double s[DIM];
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) s[a] = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    const double hi = th[m * SF_SD + i];
+#pragma unroll
+                    for (int a = 0; a < DIM; ++a) s[a] += hi * sX[a * SC + o + m];
+                }
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) res[it][a] = s[a];
+            }
+        }
+    }
+    // ================= reduced rule: a_w c (w x grad N_l)
+    {
+        const int P = ngl - 1;
+        const double *th = sd + 2 * SF_ST, *tdh = th + SF_ST;
+        const int nq = DIM == 3 ? P * P * P : P * P;
+        double w[NIT][DW];
+        __syncthreads();  // the full rule's reads of sA / sB
+        // ---- forward value passes, every component: x, y (, z), m ascending
+        {
+            double *sX = DIM == 3 ? sC : sA;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int i = si[it], o = base[it] - i;
+                double a[DW];
+#pragma unroll
+                for (int c = 0; c < DW; ++c) a[c] = 0.0;
+                for (int m = 0; m < ngl; ++m) {
+                    const double hi = th[i * SF_SD + m];
+#pragma unroll
+                    for (int c = 0; c < DW; ++c) a[c] += hi * sx[c * SC + o + m];
+                }
+#pragma unroll
+                for (int c = 0; c < DW; ++c) sX[c * SC + base[it]] = a[c];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                const int j = sj[it], o = base[it] - j * sy;
+                double a[DW];
+#pragma unroll
+                for (int c = 0; c < DW; ++c) a[c] = 0.0;
+                for (int m = 0; m < ngl; ++m) {
+                    const double hj = th[j * SF_SD + m];
+#pragma unroll
+                    for (int c = 0; c < DW; ++c) a[c] += hj * sX[c * SC + o + m * sy];
+                }
+#pragma unroll
+                for (int c = 0; c < DW; ++c) {
+                    if constexpr (DIM == 3) sB[c * SC + base[it]] = a[c];
+                    else w[it][c] = a[c];
+                }
+            }
+            if constexpr (DIM == 3) {
+                __syncthreads();
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+                    const int k = sk[it], o = base[it] - k * sz;
+                    double a[DW];
+#pragma unroll
+                    for (int c = 0; c < DW; ++c) a[c] = 0.0;
+                    for (int m = 0; m < ngl; ++m) {
+                        const double hk = th[k * SF_SD + m];
+#pragma unroll
+                        for (int c = 0; c < DW; ++c) a[c] += hk * sB[c * SC + o + m * sz];
+                    }
+#pragma unroll
+                    for (int c = 0; c < DW; ++c) w[it][c] = a[c];
+                }
+            }
+        }
+        // ---- the point: the flux a_w c eps_{acb} w_c, back to reference directions with inv J^T
+        double g[NIT][DIM][DIM];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+            const int q = (sk[it] * P + sj[it]) * P + si[it];
+            const double *gp = geoR + ((e0 + sel[it]) * nq + q) * G1;
+            const double c = gp[0];
+            double Ji[DIM][DIM];
+#pragma unroll
+            for (int b = 0; b < DIM; ++b)
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) Ji[b][k] = gp[1 + b * DIM + k];
+            double t[DW];
+#pragma unroll
+            for (int cc = 0; cc < DW; ++cc) t[cc] = c * (SF_ALPHA_W * w[it][cc]);
+            if constexpr (DIM == 3) {
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) {
+                    g[it][0][k] = Ji[2][k] * t[1] - Ji[1][k] * t[2];
+                    g[it][1][k] = Ji[0][k] * t[2] - Ji[2][k] * t[0];
+                    g[it][2][k] = Ji[1][k] * t[0] - Ji[0][k] * t[1];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) {
+                    g[it][0][k] = -(Ji[1][k] * t[0]);
+                    g[it][1][k] = Ji[0][k] * t[0];
+                }
+            }
+        }
+        __syncthreads();  // the z pass's reads of sB (3-D)
+        // ---- transposed passes, per component, as k_sumfac_elem
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) sB[k * SC + base[it]] = g[it][a][k];
+            }
+            __syncthreads();
+            if constexpr (DIM == 3) {
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    if (!(ok[it] && si[it] < P && sj[it] < P)) continue;
+                    const int k = sk[it], o = base[it] - k * sz;
+                    double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+                    for (int m = 0; m < P; ++m) {
+                        const double hk = th[m * SF_SD + k], dk = tdh[m * SF_SD + k];
+                        c0 += hk * sB[o + m * sz];
+                        c1 += hk * sB[SC + o + m * sz];
+                        c2 += dk * sB[2 * SC + o + m * sz];
+                    }
+                    sC[base[it]] = c0;
+                    sC[SC + base[it]] = c1;
+                    sC[2 * SC + base[it]] = c2;
+                }
+                __syncthreads();
+            }
+            const double *sY = DIM == 3 ? sC : sB;  // the y pass's input: (d/dx, d/dy[, h h d/dz]) parts
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!(ok[it] && si[it] < P)) continue;
+                const int j = sj[it], o = base[it] - j * sy;
+                double d0 = 0.0, d1 = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    const double hj = th[m * SF_SD + j], dj = tdh[m * SF_SD + j];
+                    d0 += hj * sY[o + m * sy];
+                    d1 += dj * sY[SC + o + m * sy];
+                    if constexpr (DIM == 3) d1 += hj * sY[2 * SC + o + m * sy];
+                }
+                sA[base[it]] = d0;
+                sA[SC + base[it]] = d1;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                if (!ok[it]) continue;
+                const int i = si[it], o = base[it] - i;
+                double s = 0.0;
+                for (int m = 0; m < P; ++m) {
+                    s += tdh[m * SF_SD + i] * sA[o + m];
+                    s += th[m * SF_SD + i] * sA[SC + o + m];
+                }
+                res[it][a] += s;
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        if (!ok[it]) continue;
+        double *out = ws + (t0 + tid + it * 256) * DIM;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) out[a] = res[it][a];
+    }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_gather_rw(int64_t N, const int32_t *__restrict__ incp,
+                                                          const int32_t *__restrict__ inc,
+                                                          const uint8_t *__restrict__ dir,
+                                                          const double *__restrict__ ws, double *__restrict__ y,
+                                                          const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    double s = 0.0;
+    if (!dir[node]) {  // (a Dirichlet row of Rw is empty: +0.0, nothing read)
+        const int j1 = incp[node + 1];
+        for (int j = incp[node]; j < j1; ++j) s += ws[(int64_t)inc[j] * DIM + a];
+    }
+    y[i] = s;
+}
+
 // the diagonal of K_e per (element, node), into ws[e][l][a]
 template <int DIM>
 __global__ __launch_bounds__(256) void k_sumfac_diag(int ngl, int nn, int64_t E, const double *__restrict__ tab,
@@ -429,6 +836,13 @@ template <int DIM>
 static void launch_sumfac(const SumfacOp *P, hipStream_t st, const double *x, double *y, const int *istate)
 {
     const unsigned ge = (unsigned)((P->E + P->neb - 1) / P->neb), gn = (unsigned)((P->N * DIM + 255) / 256);
+    if (P->which == 2) {
+        hipLaunchKernelGGL(k_sumfac_rw<DIM>, dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se, P->E,
+                           P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate);
+        hipLaunchKernelGGL(k_sumfac_gather_rw<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir,
+                           P->d_ws, y, istate);
+        return;
+    }
     hipLaunchKernelGGL(k_sumfac_elem<DIM>, dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se, P->E,
                        P->negate, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate);
     hipLaunchKernelGGL(k_sumfac_gather<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir, P->d_ws,
@@ -449,6 +863,7 @@ int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
 int sumfac_diagonal(const kle_mat *A, kle_vec *d)
 {
     const SumfacOp *P = A->sumfac;
+    if (P && P->which == 2) return fail(KLE_ERR_SUP, "getDiagonal: the sum-factorised Rw is rectangular");
     if (!P || !P->d_diag) return fail(KLE_ERR_STATE, "sum-factorised operator without tables");
     hipStream_t st = A->ctx->stream;
     KLE_HIP(hipMemcpyAsync(d->d, P->d_diag, sizeof(double) * (size_t)P->N * P->dim, hipMemcpyDeviceToDevice, st));
@@ -460,9 +875,7 @@ void sumfac_drop(kle_mat *A)
 {
     SumfacOp *P = A->sumfac;
     if (!P) return;
-    (void)hipFree(P->d_tab);
-    (void)hipFree(P->d_geoF);
-    (void)hipFree(P->d_geoR);
+    (void)hipFree(P->d_tab);  // (the geometry tables go with the last holder of P->geo)
     (void)hipFree(P->d_ws);
     (void)hipFree(P->d_diag);
     (void)hipFree(P->d_conn);
@@ -479,7 +892,7 @@ static int64_t sf_ipow(int b, int d) { return d == 2 ? (int64_t)b * b : (int64_t
 // both geometry tables (8 E (nqF + nqR) (1 + dim^2)), the 1-D tables, x read
 // once (8 n), the element results written (8 E nn dim).  k_sumfac_gather: the
 // incidence list (4 (N + 1) + 4 E nn), the Dirichlet flags (N), the element
-// results read, y written (8 m).
+// results read, y written (8 m).  Rw: the same streams with its own n.
 double sumfac_spmv_bytes(const kle_mat *A)
 {
     const SumfacOp *P = A->sumfac;
@@ -494,6 +907,7 @@ std::string sumfac_kernel_name(const kle_mat *A)
     const SumfacOp *P = A->sumfac;
     if (!P) return "?";
     const std::string d = std::to_string(P->dim);
+    if (P->which == 2) return "k_sumfac_rw<" + d + ">+k_sumfac_gather_rw<" + d + ">";
     return "k_sumfac_elem<" + d + ">+k_sumfac_gather<" + d + ">";
 }
 
@@ -535,11 +949,9 @@ int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t>
 
 using namespace kle;
 
-extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+// which: 0 K, 1 Krhs, 2 Rw
+static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
 {
-    KLE_ARG(ctx && m && out, "null arg");
-    KLE_ARG(which >= 0 && which <= 2, "which must be 0 (K) or 1 (Krhs)");
-    if (which == 2) return fail(KLE_ERR_SUP, "sum-factorised operator: Rw has no sum-factorised form here");
     if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "sum-factorised operator: no-slip meshes are not supported");
     if (m->nranks != ctx->nranks)
         return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
@@ -576,7 +988,8 @@ extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, k
     KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, dim));
     // the mask rule folded into the connectivity the element kernel reads: K
     // drops the Dirichlet entries of x, Krhs the free ones
-    for (int64_t k = 0; k < E * nn; ++k)
+    // (Rw drops nothing)
+    for (int64_t k = 0; k < E * nn && which != 2; ++k)
         if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
 
     // LDS layout: odd strides (in doubles) of the y lines, z planes and elements
@@ -603,7 +1016,7 @@ extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, k
     SumfacOp *P = new SumfacOp;
     A->ctx = ctx;
     A->sumfac = P;
-    elem_mat_fields(A, m, L, dim, dim);
+    elem_mat_fields(A, m, L, dim, which == 2 ? (dim == 2 ? 1 : 3) : dim);
     P->which = which;
     P->negate = which == 1;
     P->dim = dim;
@@ -628,17 +1041,21 @@ extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, k
     };
     // c_q and inv J of every element at both rules' points: the assembly's own
     // geometry kernel on the mesh's own corners
-    int gpF = 0, gpR = 0;
-    int rc = element_geometry(ctx, m, &P->d_geoF, &P->d_geoR, &gpF, &gpR);
-    if (!rc && (gpF != npF || gpR != npR)) rc = fail(KLE_ERR_STATE, "sum-factorised operator: geometry tables do not match the rules");
+    int rc = mesh_geometry(ctx, m, true, false, &P->geo);
+    if (!rc && (P->geo->npF != npF || P->geo->npR != npR))
+        rc = fail(KLE_ERR_STATE, "sum-factorised operator: geometry tables do not match the rules");
+    if (!rc) {
+        P->d_geoF = P->geo->F;
+        P->d_geoR = P->geo->R;
+    }
     if (!rc) rc = up(&P->d_tab, tab.data(), sizeof(double) * tab.size());
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
     if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * dim);
-    if (!rc) rc = up(&P->d_diag, nullptr, sizeof(double) * (size_t)N * dim);
-    if (!rc) {
+    if (!rc && which != 2) rc = up(&P->d_diag, nullptr, sizeof(double) * (size_t)N * dim);
+    if (!rc && which != 2) {
         // the diagonal, once: element entries into ws, gathered like a product
         const unsigned ge = (unsigned)((E * nn + 255) / 256), gn = (unsigned)((N * dim + 255) / 256);
         hipStream_t st = ctx->stream;
@@ -665,4 +1082,19 @@ extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, k
     }
     *out = A;
     return 0;
+}
+
+extern "C" int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which >= 0 && which <= 2, "which must be 0 (K) or 1 (Krhs)");
+    if (which == 2)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: Rw has its own call (kle_mat_create_rw_sumfac)");
+    return sumfac_create(ctx, m, which, out);
+}
+
+extern "C" int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    return sumfac_create(ctx, m, 2, out);
 }

@@ -18,21 +18,21 @@ from .runtime import get_ctx
 
 def kle_mat_type(kleType=None):
     """The form of the KLE matrices: the keyword, else -kle_mat_type, else
-    "assembled"; anything but assembled | element raises Error 62."""
+    "assembled"; anything but assembled | element | sumfac raises Error 62."""
     if kleType is None:
         kleType = Options().getString("kle_mat_type", "assembled")
-    if kleType not in ("assembled", "element"):
-        raise Error(62, f"-kle_mat_type {kleType}: assembled | element")
+    if kleType not in ("assembled", "element", "sumfac"):
+        raise Error(62, f"-kle_mat_type {kleType}: assembled | element | sumfac")
     return kleType
 
 
 def kle_op_type(opType=None):
     """The form of Curl, SrT and DivSrT: the keyword, else -kle_op_type, else
-    "assembled"; anything but assembled | element raises Error 62."""
+    "assembled"; anything but assembled | element | sumfac raises Error 62."""
     if opType is None:
         opType = Options().getString("kle_op_type", "assembled")
-    if opType not in ("assembled", "element"):
-        raise Error(62, f"-kle_op_type {opType}: assembled | element")
+    if opType not in ("assembled", "element", "sumfac"):
+        raise Error(62, f"-kle_op_type {opType}: assembled | element | sumfac")
     return opType
 
 
@@ -62,9 +62,14 @@ class MatFS:
         """kleType (default: -kle_mat_type, default "assembled"): "element"
         builds K, Krhs and Rw as element-wise operators and assembles nothing
         (uniform box meshes, one rank or slabs on several; anything else
-        raises Error 56).
+        raises Error 56).  "sumfac" builds them as sum-factorised operators
+        (Mat.createKLESumFactored, Mat.createRwSumFactored: any one-rank
+        mesh, unstructured included) and assembles nothing either; Rd is the
+        empty matrix and mat.kle keeps its order.
         opType (default: -kle_op_type, default "assembled"): "element" does the
-        same for Curl, SrT and DivSrT; with both, nothing at all is assembled."""
+        same for Curl, SrT and DivSrT, "sumfac" with every element's own
+        geometry on any one-rank mesh (Mat.createOperatorSumFactored); with
+        both, nothing at all is assembled."""
         if self.dom.getBoundaryType() != "FS":
             raise Error(56, "MatFS needs free-slip (Dirichlet) boundaries")
         kleType = kle_mat_type(kleType) if buildKLE else kleType
@@ -85,6 +90,15 @@ class MatFS:
             for m, n in ((self.K, "K"), (self.Krhs, "Krhs"), (self.Rw, "Rw")):
                 m.setName(n)
             self._elemK, self._elemKrhs, self._elemRw = self.K, self.Krhs, self.Rw
+            self.Rd = self._empty(dim)
+            self.kle = [self.K, self.Krhs, self.Rw, self.Rd]
+            return
+        if kleType == "sumfac":
+            # matrix-free on any one-rank mesh: the operators getSumFactoredK /
+            # Krhs / Rw return, sharing one geometry set
+            self.K, self.Krhs, self.Rw = self.getSumFactoredK(), self.getSumFactoredKrhs(), self.getSumFactoredRw()
+            for m, n in ((self.K, "K"), (self.Krhs, "Krhs"), (self.Rw, "Rw")):
+                m.setName(n)
             self.Rd = self._empty(dim)
             self.kle = [self.K, self.Krhs, self.Rw, self.Rd]
             return
@@ -145,10 +159,17 @@ class MatFS:
             self._sumfacKrhs = Mat.createKLESumFactored(self.dom.getMesh(), "Krhs")
         return self._sumfacKrhs
 
+    def getSumFactoredRw(self):
+        """Rw as a sum-factorised element-wise operator
+        (Mat.createRwSumFactored); created on first use."""
+        if getattr(self, "_sumfacRw", None) is None:
+            self._sumfacRw = Mat.createRwSumFactored(self.dom.getMesh())
+        return self._sumfacRw
+
     def buildOperators(self, opType=None):
         """Curl / SrT / DivSrT on the device (mat_fs.py:194-201): assembled
         whatever the kleType, unless opType (default: -kle_op_type) is
-        "element"."""
+        "element" or "sumfac"."""
         self.operator = Operators()
         self.operator.setDimensions(self.dom.getDimensions())
         self.operator.build(self.dom.getMesh(), opType)
@@ -174,18 +195,20 @@ class MatNS(MatFS):
         self._Ksum = None
 
     def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None, nsType=None):
-        """opType "element" (default: -kle_op_type): Curl, SrT and DivSrT as
-        element-wise operators, which carry no boundary rule.
+        """opType "element" or "sumfac" (default: -kle_op_type): Curl, SrT and
+        DivSrT as element-wise operators, which carry no boundary rule
+        ("sumfac": any one-rank mesh; the NS matrices stay assembled).
         nsType (default: -kle_ns_type, default "assembled"): "element" builds
         K, Krhs, Rw, Kfs, Krhsfs, Rwfs and K + Kfs as element-wise operators
         (Mat.createNSElement) and never calls kle_assemble_ns; Rd and Rdfs are
         empty assembled matrices and mat.kle keeps its order of eight.  Uniform
         box meshes, one rank or slabs on several; anything else raises Error
         56.  This switch is the way to the matrix-free no-slip system:
-        kleType="element" / -kle_mat_type element name the free-slip form,
-        which a no-slip mesh does not have, and keep raising Error 56 here."""
-        if kle_mat_type(kleType) == "element":
-            raise Error(56, "-kle_mat_type element: no-slip matrices have no element-wise form")
+        kleType="element" / -kle_mat_type element (and "sumfac") name the
+        free-slip forms, which a no-slip mesh does not have, and keep raising
+        Error 56 here."""
+        if kle_mat_type(kleType) in ("element", "sumfac"):
+            raise Error(56, f"-kle_mat_type {kle_mat_type(kleType)}: no-slip matrices have no such form")
         if self.dom.getBoundaryType() != "NS":
             raise Error(56, "MatNS needs no-slip boundaries")
         nsType = kle_ns_type(nsType) if buildKLE else nsType
@@ -235,7 +258,8 @@ class Operators:
     same ascending-cell ADD order.  With opType "element" (-kle_op_type
     element) nothing is assembled: the three are element-wise operators
     (Mat.createOperatorElement; uniform box meshes, one rank or slabs on
-    several)."""
+    several).  With opType "sumfac" they read every element's own geometry
+    (Mat.createOperatorSumFactored; any one-rank mesh)."""
 
     def __init__(self):
         self.Curl = self.SrT = self.DivSrT = None
@@ -244,8 +268,10 @@ class Operators:
         self.dim, self.dim_w, self.dim_s = dims
 
     def build(self, mesh, opType=None):
-        if kle_op_type(opType) == "element":
-            self.Curl, self.SrT, self.DivSrT = (Mat.createOperatorElement(mesh, n) for n in ("Curl", "SrT", "DivSrT"))
+        opType = kle_op_type(opType)
+        if opType in ("element", "sumfac"):
+            create = Mat.createOperatorElement if opType == "element" else Mat.createOperatorSumFactored
+            self.Curl, self.SrT, self.DivSrT = (create(mesh, n) for n in ("Curl", "SrT", "DivSrT"))
             for m, n in ((self.Curl, "Curl"), (self.SrT, "SrT"), (self.DivSrT, "DivSrT")):
                 m.setName(n)
             return

@@ -416,7 +416,7 @@ class Mat:
         matrix.  mult, *, multAdd, createVecLeft/Right, getDiagonal, the size
         getters, getInfo, spmvKernel, timeLocalSpmv and KSP.setOperators work
         as on createKLEElement's operators; calls that need stored values and
-        copyDirichletRows raise Error 56, as do which="Rw", no-slip meshes,
+        copyDirichletRows raise Error 56, as do which="Rw" (createRwSumFactored), no-slip meshes,
         several ranks and a mesh partitioned for another rank count than the
         context's; any other `which` raises Error 62."""
         kinds = {"K": 0, "Krhs": 1, "Rw": 2}
@@ -426,6 +426,45 @@ class Mat:
         h = C.c_void_p()
         call("kle_mat_create_kle_sumfac", ctx.h, mesh._h, kinds[which], C.byref(h))
         m = cls._wrap(h, ctx, mesh, mesh.dim, mesh.dim)
+        m.setName("sum-factorised " + which)
+        return m
+
+    @classmethod
+    def createRwSumFactored(cls, mesh):
+        """Sum-factorised element-wise Rw [dim N x dim_w N] of any one-rank
+        mesh, uniform box or unstructured (kle_mat_create_rw_sumfac): a
+        quadrature-point evaluation sharing the geometry tables of
+        createKLESumFactored's K and Krhs on the same mesh; Dirichlet rows are
+        +0.0.  mult, *, multAdd, createVecLeft/Right, the size getters,
+        getInfo, spmvKernel and timeLocalSpmv work; getDiagonal,
+        copyDirichletRows and calls that need stored values raise Error 56, as
+        do no-slip meshes, several ranks and a mesh partitioned for another
+        rank count than the context's."""
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_rw_sumfac", ctx.h, mesh._h, C.byref(h))
+        m = cls._wrap(h, ctx, mesh, mesh.dim, 1 if mesh.dim == 2 else 3)
+        m.setName("sum-factorised Rw")
+        return m
+
+    @classmethod
+    def createOperatorSumFactored(cls, mesh, which="Curl"):
+        """Element-wise Curl, SrT or DivSrT with every element's own geometry,
+        on any one-rank mesh, uniform box or unstructured, free-slip or no-slip
+        (kle_mat_create_operator_sumfac): the products of
+        createOperatorElement with a nodal geometry table over all elements and
+        a gather over a CSR incidence list (any valence).  Same call surface;
+        several ranks and a mesh partitioned for another rank count than the
+        context's raise Error 56, any other `which` Error 62."""
+        kinds = {"Curl": 0, "SrT": 1, "DivSrT": 2}
+        if which not in kinds:
+            raise Error(62, f"createOperatorSumFactored: which must be 'Curl', 'SrT' or 'DivSrT', not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_operator_sumfac", ctx.h, mesh._h, kinds[which], C.byref(h))
+        dim_w, dim_s = (1, 3) if mesh.dim == 2 else (3, 6)
+        rbs, cbs = {"Curl": (dim_w, mesh.dim), "SrT": (dim_s, mesh.dim), "DivSrT": (mesh.dim, dim_s)}[which]
+        m = cls._wrap(h, ctx, mesh, rbs, cbs)
         m.setName("sum-factorised " + which)
         return m
 

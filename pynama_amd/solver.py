@@ -32,6 +32,13 @@ class KspSolver(KSP):
 
 
 class KleSolver:
+    """solve(): after a matrix-free build with the element-wise operators of a
+    box mesh (-kle_mat_type element) the Dirichlet values are copied back
+    exactly (Mat.copyDirichletRows).  After a sum-factorised build
+    (-kle_mat_type sumfac), whose operators hold no such call, they are held to
+    the solve's rtol, as in the assembled solve and as with -kle_k_type
+    sumfac."""
+
     def __init__(self):
         self.mat = None
         self._b = None
@@ -58,8 +65,12 @@ class KleSolver:
         self._Rw = self.mat.getElementRw() if ktype == "element" else None
         if ktype == "sumfac":
             self._Krhs = self.mat.getSumFactoredKrhs()
-        # matrix-free build: solve() hands back the Dirichlet values exactly
-        self._exactBC = K.getFormat() == "elem"
+        # matrix-free build (-kle_mat_type element): solve() hands back the
+        # Dirichlet values exactly.  The sum-factorised operators refuse
+        # copyDirichletRows, so after a sumfac build the Dirichlet values are
+        # held to the solve's rtol, as in the assembled solve and with
+        # -kle_k_type sumfac.
+        self._exactBC = K.getFormat() == "elem" and "k_sumfac" not in K.spmvKernel()
         self.solver = KspSolver()
         self.solver.createSolver(self.mat.getElementK() if ktype == "element"
                                  else self.mat.getSumFactoredK() if ktype == "sumfac" else K)

@@ -86,8 +86,25 @@ assembled and with the sum-factorised operators (-kle_k_type sumfac) to rtol
 1e-10, iterations and the true residual K u - (Rw w + Krhs u_bc) through the
 assembled matrices.
 
+With --sumfac-system the legs are those of the whole matrix-free set on an
+unstructured mesh (-kle_mat_type sumfac -kle_op_type sumfac: K, Krhs, Rw,
+Curl, SrT, DivSrT; records to profiles/elem/sumfac_system.jsonl), one process,
+the forms alternating round by round, on perturbed_box(3, nelem, seed=5) of
+the first mesh and on the box of the same size (there also the `element`
+forms):
+
+  build_system   wall time and device memory (hipMemGetInfo before / after) of
+                 MatFS.build per form
+  product_<op>   --reps products of Rw, Curl, SrT, DivSrT per form, with the
+                 algorithmic bytes (spmv_bytes)
+  chain          the evalRHS chain without the KLE solve
+  eval_rhs       one whole BaseProblem.evalRHS per form (wall time, iterations)
+
+With --check: Taylor-Green with the matrix-free set to rtol 1e-10, the true
+residual K u - (Rw w + Krhs u_bc) formed through the assembled K, Krhs and Rw.
+
   python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
-                          [--matfree | --operators [--config4] | --noslip | --sumfac]
+                          [--matfree | --operators [--config4] | --noslip | --sumfac | --sumfac-system]
 """
 import argparse
 import ctypes as C
@@ -438,6 +455,136 @@ def sumfac(a, pa, np, hip, ctx, emit):
                           true_rel_residual_assembled=r.norm() / rhs.norm()))
                 del sol
         del ksps, ops, Ks, mat, dom, x, y, b
+        gc.collect()
+
+
+def sumfac_system(a, pa, np, hip, ctx, emit):
+    import tempfile
+
+    from pynama_amd._lib import call
+    from pynama_amd.meshgen import perturbed_box, write_gmsh
+    from pynama_amd.petsc import Options
+    ne_s, ngl = a.meshes[0].split(":")
+    nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+    dim = len(nelem)
+    tg = "taylor_green3d" if dim == 3 else "taylor_green"
+    bc = {"custom-func": {"name": tg}}
+    path = os.path.join(tempfile.mkdtemp(prefix="kle_sumfac_system_"), "mesh.msh")
+    write_gmsh(path, dim, *perturbed_box(dim, nelem, seed=5))
+    domains = {"unstructured": {"ngl": ngl, "gmsh-file": path},
+               "box": {"ngl": ngl, "box-mesh": {"nelem": nelem, "lower": [0.0] * dim, "upper": [1.0] * dim}}}
+    names = ("Rw",) + OPS
+
+    def get(mat, nm):
+        return mat.Rw if nm == "Rw" else getattr(mat.getOperators(), nm)
+
+    for leg, domain in domains.items():
+        forms = ("assembled", "sumfac") + (("element",) if leg == "box" else ())
+        dom = pa.Domain()
+        dom.configure({"domain": domain, "boundary-conditions": bc})
+        dom.setUp()
+        base = {"mesh": leg, "nelem": nelem, "ngl": ngl, "nodes": dom.mesh.N, "rounds": a.rounds}
+        mats = {}
+        for form in forms:
+            gc.collect()
+            ctx.synchronize()
+            m0, t0 = hip.free_bytes(), time.perf_counter()
+            mat = pa.MatFS()
+            mat.setDomain(dom)
+            mat.build(kleType=form, opType=form)
+            ctx.synchronize()
+            t1 = time.perf_counter()
+            mats[form] = mat
+            emit(dict(base, leg="build_system", form=form, ms=1e3 * (t1 - t0),
+                      device_bytes_K_Krhs_Rw_Curl_SrT_DivSrT=m0 - hip.free_bytes(),
+                      formats=[mat.K.getFormat(), mat.Krhs.getFormat()] + [get(mat, n).getFormat() for n in names]))
+        ratios = {}
+        for nm in names:
+            ops = {form: get(mats[form], nm) for form in forms}
+            x = ops["sumfac"].createVecRight()
+            x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+            y = ops["sumfac"].createVecLeft()
+            t_prod = {k: [] for k in forms}
+            for _ in range(a.rounds):
+                for label, A in ops.items():
+                    for _w in range(20):
+                        A.mult(x, y)
+                    ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                    t_prod[label].append(1e3 * ms / a.reps)
+            for label, A in ops.items():
+                emit(dict(base, leg="product_" + nm, form=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                          reps=a.reps, us=spread(t_prod[label]),
+                          tb_per_s=A.spmvBytes() / statistics.median(t_prod[label]) * 1e-6))
+            ratios[nm] = {f + "_over_sumfac": statistics.median(t_prod[f]) / statistics.median(t_prod["sumfac"])
+                          for f in forms if f != "sumfac"}
+            ratios[nm]["sumfac_faster_than_assembled_beyond_spread"] = bool(max(t_prod["sumfac"]) < min(t_prod["assembled"]))
+        chains = {form: Chain(mats[form].getOperators(), dim) for form in forms}
+        f = pa.fields.get(tg)
+        vel = mats["sumfac"].K.createVecRight()
+        vel.setArray(np.asarray(f.velocity(dom.getFullCoordArray(), 1.0), dtype=np.float64).ravel())
+        rhs, fo = vel.duplicate(), mats["sumfac"].getOperators().Curl.createVecLeft()
+        t_chain = {k: [] for k in forms}
+        for _ in range(a.rounds):
+            for label, ch in chains.items():
+                for _w in range(10):
+                    eval_rhs_chain(call, ch, vel, rhs, fo)
+                ms = hip.timed_ms(lambda: [eval_rhs_chain(call, ch, vel, rhs, fo) for _r in range(a.reps)])
+                t_chain[label].append(ms / a.reps)
+        for label in forms:
+            emit(dict(base, leg="chain", form=label, steps="computeVtensV, SrT, scale, axpy, DivSrT, scale, Curl",
+                      reps=a.reps, ms=spread(t_chain[label])))
+        ratios["chain"] = {f + "_over_sumfac": statistics.median(t_chain[f]) / statistics.median(t_chain["sumfac"])
+                           for f in forms if f != "sumfac"}
+        emit(dict(base, leg="ratio_system", **ratios))
+        del chains, rhs, fo
+        # one whole evalRHS per form: a BaseProblem of its own
+        cfg = {"name": "sumfac_system", "material-properties": {"rho": 0.5, "mu": 0.01}, "domain": domain,
+               "boundary-conditions": bc, "initial-conditions": bc}
+        for form in forms:
+            opts = Options()
+            opts.setValue("kle_mat_type", form)
+            opts.setValue("kle_op_type", form)
+            try:
+                prob = pa.BaseProblem(cfg)
+                prob.setUp()
+                prob.setUpSolver()
+            finally:
+                opts.delValue("kle_mat_type")
+                opts.delValue("kle_op_type")
+            fo = prob.operator.Curl.createVecLeft()
+            prob.evalRHS(None, 0.0, prob.vort, fo)  # warm-up
+            walls = []
+            for _ in range(a.rounds):
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                prob.evalRHS(None, 0.0, prob.vort, fo)
+                ctx.synchronize()
+                walls.append(1e3 * (time.perf_counter() - t0))
+            ksp = prob.solverKLE.getKSP()
+            emit(dict(base, leg="eval_rhs", form=form, wall_ms=spread(walls), kle_iterations=ksp.getIterationNumber(),
+                      kle_reason=ksp.getConvergedReason(), finite=bool(np.all(np.isfinite(fo.getArray())))))
+            del prob, fo
+            gc.collect()
+        if a.check and leg == "unstructured":
+            asm, mf = mats["assembled"], mats["sumfac"]
+            sol = pa.KleSolver()
+            sol.setMat(mf)
+            sol.setUp()
+            vort = mf.Rw.createVecRight()
+            vort.setArray(np.asarray(f.vorticity(dom.getFullCoordArray(), 1.0), dtype=np.float64).ravel())
+            vel = sol.getSolution()
+            dom.applyBoundaryConditions(vel, "velocity", 0.0, 0.02)
+            rhs = asm.Rw * vort
+            rhs.axpy(1.0, asm.Krhs * vel)  # vel holds u_bc on the Dirichlet nodes; Krhs reads nothing else
+            sol.solve(vort)
+            ksp = sol.getKSP()
+            r = asm.K * vel
+            r.aypx(-1.0, rhs)
+            emit(dict(base, leg="check_solve", form="sumfac", operator=ksp.getOperators()[0].spmvKernel(),
+                      rw=mf.Rw.spmvKernel(), iterations=ksp.getIterationNumber(), reason=ksp.getConvergedReason(),
+                      rtol=1e-10, true_rel_residual_assembled=r.norm() / rhs.norm()))
+            del sol
+        del mats, dom, vel
         gc.collect()
 
 
@@ -831,13 +978,17 @@ def main():
     ap.add_argument("--sumfac", action="store_true",
                     help="the sum-factorised K: the first mesh as bench.py's unstructured mesh (vs the assembled K) "
                          "and as a box (vs the dense-GEMM element K)")
+    ap.add_argument("--sumfac-system", action="store_true",
+                    help="the whole matrix-free set (K, Krhs, Rw, Curl, SrT, DivSrT) on the first mesh as an "
+                         "unstructured mesh and as a box: builds, products, the evalRHS chain, one evalRHS")
     ap.add_argument("--fallback-meshes", nargs="*", default=["16,12,12:5", "12,10,10:5", "8,8,6:5"],
                     help="with --noslip: tried in order where the assembled no-slip set cannot be built")
     ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree, "
                                                 "operators.jsonl with --operators, noslip.jsonl with --noslip)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "elem", "sumfac.jsonl" if a.sumfac else "noslip.jsonl" if a.noslip else
+        a.out = os.path.join(ROOT, "profiles", "elem", "sumfac_system.jsonl" if a.sumfac_system else
+                             "sumfac.jsonl" if a.sumfac else "noslip.jsonl" if a.noslip else
                              "operators.jsonl" if a.operators else
                              "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
     import numpy as np
@@ -854,6 +1005,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.sumfac_system:
+        sumfac_system(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     if a.sumfac:
         sumfac(a, pa, np, hip, ctx, emit)
         fout.close()
