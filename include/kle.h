@@ -129,7 +129,10 @@ const char *kle_last_error(void);
  *                         repeats a few distinct rows over the lattice -- are stored once; proposed by a
  *                         hash, decided by comparison, kept only where it saves at least half of the
  *                         bricked bytes and fits the descriptors' 1 GiB; the product is bitwise the same;
- *                         0 every row's own stream
+ *                         0 every row's own stream.  On the full layout the units (pairs of rows) whose rows
+ *                         share boxes and values are then ordered class by class and handed to the waves in
+ *                         runs of up to 4: an item's nine values and block positions are formed once per run
+ *                         (kle_mat_get_brick_runs; taken where at most 3/4 of the items then load their values)
  *   "spmv_brick_dedup_full" 0, 1* [build]: a K whose rows are shared keeps the full 9-entry blocks -- read
  *                         from the caches, the kernel is bound by its instructions and the compact stream's
  *                         offsets cost more than its bytes save; the full layout is built first and the
@@ -264,6 +267,19 @@ int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, in
  * array: refused too (shared values have one common base, 0).
  * out[3]: rows in bricks, rows stored, doubles of the unique array. */
 int kle_brick_plan_box_shared(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int shift, long long *out);
+/* Diagnostic, host only: the plan under the forced split `split` (as
+ * "spmv_brick_split"; 0 planned) with that rewrite, then its units grouped
+ * into runs of at most G units of one class as the brick SpMV groups them on a
+ * shared full-layout K (a class: the units whose two rows have the same packed
+ * boxes and value offsets -- they stream identical items, so a wave loads an
+ * item's values once for the whole run), checked by the same validator: every
+ * run inside its brick's units, 1 <= count <= G, every unit in exactly one
+ * run, all units of a run of one class.  corrupt 1 moves a unit into a run of
+ * another class, 2 lengthens the first run by one: both refused (KLE_ERR_SUP).
+ * out[6]: units, classes summed over the bricks, runs, 64-lane items, items
+ * whose values are loaded, units of the largest run. */
+int kle_brick_plan_box_runs(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int split, int G, int corrupt,
+                            long long *out);
 /* Per-kernel HIP-event timing of the hot kernels (SpMV, CG updates). */
 int kle_ctx_set_profiling(kle_ctx *ctx, int on);
 /* Time only the launches tagged `name` ("spmv", "dot", "cg_update", "reduce",
@@ -786,6 +802,12 @@ int kle_mat_get_brick_compact(const kle_mat *A, int *compact, long long *dropped
  * (each row padded to 16 doubles); 0, 0, 0 otherwise.  kle_mat_spmv_bytes
  * still counts what the kernel's loads request, not what reaches HBM. */
 int kle_mat_get_brick_dedup(const kle_mat *A, int *dedup, long long *unique_rows, long long *unique_bytes);
+/* The runs of a shared full-layout K (units of one class next to each other,
+ * an item's values loaded once per run of at most run_cap units): the cap, the
+ * runs, the units, the 64-lane items and the items whose values are loaded;
+ * all 0 where the product takes no runs. */
+int kle_mat_get_brick_runs(const kle_mat *A, int *run_cap, long long *runs, long long *units, long long *items,
+                           long long *item_loads);
 /* N > 1: run the rows that read no ghost entry while the halo exchange is in
  * flight on a second stream (default on). */
 int kle_mat_set_halo_overlap(kle_mat *A, int on);

@@ -68,6 +68,7 @@ _SIGS = {
                            C.POINTER(C.c_double)],
     "kle_brick_plan_box_shared": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(C.c_longlong)],
+    "kle_brick_plan_box_runs": [C.c_int] * 9 + [C.POINTER(C.c_longlong)],
     "kle_ctx_enable_ipc": [vp],
     "kle_ctx_set_profiling": [vp, C.c_int],
     "kle_ctx_set_profiling_sample": [vp, C.c_int],
@@ -162,6 +163,7 @@ _SIGS = {
     "kle_mat_get_symmetric": [vp, C.POINTER(C.c_int)],
     "kle_mat_get_brick_compact": [vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)],
     "kle_mat_get_brick_dedup": [vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+    "kle_mat_get_brick_runs": [vp, C.POINTER(C.c_int)] + [C.POINTER(C.c_longlong)] * 4,
     "kle_mat_get_sym_bricks": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)],
     "kle_get_nb_pad": [],

@@ -32,6 +32,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kle_brick.hpp"
@@ -65,6 +66,19 @@ __device__ __forceinline__ BItem bitem(int s, int muP, int muQ, int irP, int irQ
     return {1, irP | irQ << 16, muP | muQ << 16, kbP | kbQ << 16, s | eP << 8 | eQ << 9};
 }
 constexpr int BI_NEWP = 1024;  // (sf: the item starts row P -- its x into the row registers)
+constexpr int BI_PB = 2048;    // (sf, runs: row P is the unit's second row -- its full passes)
+// (runs: the record also carries the run's units, n of them, and their region
+// indices irA | irB << 16, as the cursor may be at the next run when the item is summed)
+template <int G>
+struct BItemG : BItem {
+    int n;
+    int iu[G];
+    __device__ __forceinline__ BItemG &operator=(const BItem &b)
+    {
+        BItem::operator=(b);
+        return *this;
+    }
+};
 
 // FF: the first item's registers are in flight when the item loop starts,
 // which holds only while the compiler does not copy them on the way there
@@ -95,7 +109,17 @@ constexpr int BI_NEWP = 1024;  // (sf: the item starts row P -- its x into the r
 // address and the distance from P to Q.  NTL: nontemporal value loads (the
 // full stream is read once per product; a deduplicated one is re-read by
 // every brick and may stay cached).
-template <int WV, bool FF = true, bool DOT = false, bool CP = false, bool DD = false, bool NTL = true>
+// G > 0 (DD, full layout, no DOT): runs of same-class units (kle_brick.hpp
+// brick_runs_build).  A wave takes a run -- up to G units that stream the
+// identical items and differ only in their rows' region indices -- instead of
+// a unit; the issue cursor walks the class's items once, so an item's nine
+// values are loaded and its lanes' block positions in the box are computed
+// once, and the summed item is applied to each unit of the run in turn:
+// rr = (block position - the row's own) + the unit's region index, the
+// unit's x and sums, exactly the arithmetic of a unit on its own.  rowd then
+// holds the runs' records (brick_run_words(G) ints each, rstride per brick)
+// and bd[b].nrun the brick's runs.
+template <int WV, bool FF = true, bool DOT = false, bool CP = false, bool DD = false, bool NTL = true, int G = 0>
 __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly, int Lz, int zo, int hp, int rstride,
                                                                  const BrickDesc *__restrict__ bd,
                                                                  const int2 *__restrict__ rowd,
@@ -105,8 +129,11 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
                                                                  double *__restrict__ dpart,
                                                                  const int *__restrict__ istate KLE_PROBE_PARAM)
 {
+    static_assert(G == 0 || (DD && !CP && !DOT), "runs: the full layout of a deduplicated array, no DOT");
     KLE_PROBE_CONST
     constexpr int NT = 64 * WV;
+    constexpr int GG = G > 0 ? G : 1, RW = brick_run_words(GG);
+    using Item = std::conditional_t<(G > 0), BItemG<GG>, BItem>;
     constexpr int D = 1;  // items in flight ahead of the summed one
     extern __shared__ double lds[];
     KLE_PROBE_TS(ts0)
@@ -116,7 +143,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
 #endif
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int NU = bd[b].nr / 2;  // units of two rows (kle_brick_plan.cpp)
+    const int NU = G > 0 ? bd[b].nrun : bd[b].nr / 2;  // units of two rows (kle_brick_plan.cpp); G: runs of them
     const int ox = bd[b].ox, oy = bd[b].oy, oz = bd[b].oz, RX = bd[b].RX, RY = bd[b].RY, RZ = bd[b].RZ;
     const int eb = bd[b].eb;
     const long long vbase = bd[b].vbase, wsoff = bd[b].wsoff;
@@ -194,7 +221,11 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // (the brick's rows at a fixed stride: their descriptors' address needs
     // no load, so their scalar loads go out beside bd's; address-space
     // cast: scalar loads)
-    cint *rdesc = (cint *)(rowd + (int64_t)b * rstride);
+    // (G: the brick's run records, UW ints each -- the class's four words,
+    // the count, the units' region indices)
+    constexpr int UW = G > 0 ? RW : 4;
+    cint *rdesc = G > 0 ? (cint *)(reinterpret_cast<const int *>(rowd) + (int64_t)b * rstride * RW)
+                        : (cint *)(rowd + (int64_t)b * rstride);
     const double *vb = sval + vbase;
     // a row from its descriptor (kle_brick.hpp): packed box (dbx, dby, dbz,
     // bnx, bny, bnz: 4 bits each) + the low byte of its region index; value
@@ -313,8 +344,21 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         ki = 0;
         oa = ob = 0;
     };
+    // G: the run at the cursor (its units, their irA | irB << 16) and the
+    // next one's, fetched ahead with its class's descriptors
+    int rcnt = 1, rir[GG], pcnt = 1, pir[GG];
+#pragma unroll
+    for (int g = 0; g < GG; ++g) rir[g] = pir[g] = 0;
+    auto run_units = [&](int u, int &cnt, int *ir) {
+        if constexpr (G > 0) {
+            cnt = rdesc[UW * u + 4];
+#pragma unroll
+            for (int g = 0; g < GG; ++g) ir[g] = rdesc[UW * u + 5 + g];
+        }
+    };
     if (!idone) {
-        unit_setup(w, rdesc[4 * w], rdesc[4 * w + 1], rdesc[4 * w + 2], rdesc[4 * w + 3]);
+        unit_setup(w, rdesc[UW * w], rdesc[UW * w + 1], rdesc[UW * w + 2], rdesc[UW * w + 3]);
+        run_units(w, rcnt, rir);
     } else {
         A.v = vb;
         A.mu = 1;
@@ -336,16 +380,22 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     // (a brick without rows, NU = 0, reads its slot's first unit: the table
     // holds at least one unit per brick)
     const int u0 = max(0, min(pend, NU - 1));
-    int pd0 = rdesc[4 * u0], pd1 = rdesc[4 * u0 + 1];
-    int pd2 = rdesc[4 * u0 + 2], pd3 = rdesc[4 * u0 + 3];
+    int pd0 = rdesc[UW * u0], pd1 = rdesc[UW * u0 + 1];
+    int pd2 = rdesc[UW * u0 + 2], pd3 = rdesc[UW * u0 + 3];
+    run_units(u0, pcnt, pir);
     // the item at the cursor: its loads into vn, its record; the cursor then
     // moves on (past the last unit it stays, re-reading the last item)
-    auto issue = [&](double *vn, int &rn, BItem &itn) {
+    auto issue = [&](double *vn, int &rn, Item &itn) {
         int zp, zq;
         if (idone) {  // (a re-read of A's first pass: cache hits, the results go nowhere)
             load_v(A, A, 0, 0, 64, vn, rn, 0, 0, zp, zq);
             itn.ok = 0;
             return;
+        }
+        if constexpr (G > 0) {
+            itn.n = rcnt;
+#pragma unroll
+            for (int g = 0; g < GG; ++g) itn.iu[g] = rir[g];
         }
         if (ph == 0) {  // A's passes
             load_v(A, A, ki, 0, 64, vn, rn, oa, 0, zp, zq);
@@ -366,6 +416,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
             load_v(B, B, ki, 0, 64, vn, rn, ob, 0, zp, zq);
             ob += zp;
             itn = bitem(64, B.mu, B.mu, B.ir, B.ir, ki, 0, ki + 64 >= bend, 0);
+            if constexpr (G > 0) itn.sf |= BI_PB;
             ki += 64;
             if (ki >= bend) ph = 3;
         }
@@ -374,18 +425,24 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
                 idone = true;
             } else {
                 unit_setup(pend, pd0, pd1, pd2, pd3);
+                if constexpr (G > 0) {
+                    rcnt = pcnt;
+#pragma unroll
+                    for (int g = 0; g < GG; ++g) rir[g] = pir[g];
+                }
                 pend = take();
                 const int u = max(0, min(pend, NU - 1));
-                pd0 = rdesc[4 * u];
-                pd1 = rdesc[4 * u + 1];
-                pd2 = rdesc[4 * u + 2];
-                pd3 = rdesc[4 * u + 3];
+                pd0 = rdesc[UW * u];
+                pd1 = rdesc[UW * u + 1];
+                pd2 = rdesc[UW * u + 2];
+                pd3 = rdesc[UW * u + 3];
+                run_units(u, pcnt, pir);
             }
         }
     };
     double v0[9], v1[9];
     int r0 = 0, r1 = 0;
-    BItem i0, i1;
+    Item i0, i1;
 #ifdef KLE_PROBE_BUILD
     unsigned long long tsf = 0;
 #endif
@@ -497,10 +554,64 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
         };
         // one step: issue the next item into vn, wait for vv (the D newer
         // items stay in flight), sum it
-        auto step = [&](double *vv, const int rrk, const BItem &it, double *vn, int &rn, BItem &itn) {
+        // (G: the direct sums of the run's units, each unit's as on its own)
+        double ag[GG][3];
+#pragma unroll
+        for (int g = 0; g < GG; ++g) ag[g][0] = ag[g][1] = ag[g][2] = 0.0;
+        auto step = [&](double *vv, const int rrk, const Item &it, double *vn, int &rn, Item &itn) {
             const int rr = CP ? rrk & 0xFFFF : rrk;
             issue(vn, rn, itn);
             if (!it.ok) return false;
+            if constexpr (G > 0) {
+                // the item once for every unit of its run: the lanes' rows
+                // and blocks are the class's, rr the block's place relative
+                // to the row's own (row_setup with a region index of 0)
+                const int is = it.sf & 255;
+                const bool q = lane >= is;
+                const int kk = q ? (int)((unsigned)it.kb >> 16) + lane - is : (it.kb & 0xFFFF) + lane;
+                const bool live = kk < (q ? (int)((unsigned)it.mu >> 16) : (it.mu & 0xFFFF));
+                const bool tl = live && kk > 0, mine = live && !q, qs = live && q;
+#pragma unroll
+                for (int g = 0; g < GG; ++g) {
+                    if (g < it.n) {
+                        // (row P: the unit's first row, or its second in that row's full passes)
+                        const int irQ = (int)((unsigned)it.iu[g] >> 16), irP = it.sf & BI_PB ? irQ : it.iu[g] & 0xFFFF;
+                        // x of the lane's row (one address per part: a broadcast read) and of its block's column
+                        const int irl = q ? irQ : irP, rg = rr + irl;
+                        const double c0 = xl[irl], c1 = xl[RN + irl], c2 = xl[2 * RN + irl];
+                        const double xj0 = xl[rg], xj1 = xl[RN + rg], xj2 = xl[2 * RN + rg];
+                        if (g == 0) sym_wait9<9 * D>(vv);
+                        const int rt = tl ? rg : RN + lane;
+                        const double s0 = vv[0] * xj0 + vv[1] * xj1 + vv[2] * xj2;
+                        const double s1 = vv[3] * xj0 + vv[4] * xj1 + vv[5] * xj2;
+                        const double s2 = vv[6] * xj0 + vv[7] * xj1 + vv[8] * xj2;
+                        const double t0 = vv[0] * c0 + vv[3] * c1 + vv[6] * c2;
+                        const double t1 = vv[1] * c0 + vv[4] * c1 + vv[7] * c2;
+                        const double t2 = vv[2] * c0 + vv[5] * c1 + vv[8] * c2;
+                        if (!(probe & 1)) {  // (timing probe 1: no transposed adds)
+                            atomicAdd(&acc[rt], fx_of(t0 * S1, S2));
+                            atomicAdd(&acc[RS + rt], fx_of(t1 * S1, S2));
+                            atomicAdd(&acc[2 * RS + rt], fx_of(t2 * S1, S2));
+                        } else if (!live) {
+                            acc[RN + lane] += (unsigned long long)(t0 + t1 + t2);
+                        }
+                        ag[g][0] += mine ? s0 : 0.0;
+                        ag[g][1] += mine ? s1 : 0.0;
+                        ag[g][2] += mine ? s2 : 0.0;
+                        if (it.sf & 256) {
+                            row_out(irP, ag[g][0], ag[g][1], ag[g][2], c0, c1, c2);
+                            ag[g][0] = qs ? s0 : 0.0;  // (Q's lanes start Q's sum)
+                            ag[g][1] = qs ? s1 : 0.0;
+                            ag[g][2] = qs ? s2 : 0.0;
+                            if (it.sf & 512) {
+                                row_out(irQ, ag[g][0], ag[g][1], ag[g][2], c0, c1, c2);
+                                ag[g][0] = ag[g][1] = ag[g][2] = 0.0;
+                            }
+                        }
+                    }
+                }
+                return true;
+            }
             const int is = it.sf & 255, irP = it.ir & 0xFFFF, irQ = (int)((unsigned)it.ir >> 16);
             const bool q = lane >= is;
             // x of the lane's row (P's below s, Q's from s on); the row
@@ -1017,6 +1128,12 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
     }
     for (BrickDesc &D : bp.bricks) D.vbase = 0;
     bp.dedup = true;
+    // units class by class, handed out as runs (the full layout: a unit's
+    // items depend on its rows' boxes and value offsets alone)
+    if (!compact) {
+        brick_runs_build(bp, BRICK_RUN_G);
+        if (!brick_runs_pay(bp.run_item_loads, bp.run_items)) brick_runs_clear(bp);  // (too little repeats inside the bricks)
+    }
     A->brick_dedup = 1;
     A->brick_unique_rows = kept;
     A->brick_unique_bytes = ubytes;
@@ -1099,6 +1216,46 @@ int brick_finish(kle_mat *A, void *plan)
         KLE_TRY(h2d(A->d_browd, pad.data(), sizeof(int) * pad.size()));
     }
     A->brick_rstride = rstride;
+    if (!bp->runs.empty()) {
+        // the runs' records, brick q's at q rs (as the row descriptors): the
+        // class's four descriptor words without their region-index bytes, the
+        // count, each unit's irA | irB << 16 -- all taken from the validated
+        // descriptors and runs; the slots past a brick's runs are never read
+        // (every read is of a run < nrun)
+        const int G = bp->run_cap, RW = brick_run_words(G);
+        int rs = 1;
+        for (const BrickDesc &D : bp->bricks) rs = std::max(rs, D.nrun);
+        std::vector<int> rec((size_t)NB * rs * RW, 0);
+        for (int q = 0; q < NB; ++q) {
+            const BrickDesc &D = bp->bricks[q];
+            for (int r = 0; r < D.nrun; ++r) {
+                int *o = rec.data() + ((size_t)q * rs + r) * RW;
+                const int rv = bp->runs[bp->run_first[q] + r];
+                const int first = brick_run_first(rv), cnt = brick_run_count(rv);
+                const int *ord = bp->run_order.data() + D.rstart / 2 + first;
+                const int64_t r0 = (int64_t)D.rstart + 2 * ord[0];
+                for (int k = 0; k < 4; ++k) o[k] = bp->rowd[2 * r0 + k] & 0xFFFFFF;
+                o[4] = cnt;
+                for (int g = 0; g < cnt; ++g) {
+                    const int64_t ra = (int64_t)D.rstart + 2 * ord[g];
+                    const int irb = brick_row_null(bp->rowd.data(), ra + 1) ? 0 : brick_row_ir(bp->rowd.data(), ra + 1);
+                    o[5 + g] = brick_row_ir(bp->rowd.data(), ra) | irb << 16;
+                }
+            }
+        }
+        if (hipMalloc(&A->d_bruns, sizeof(int) * std::max<size_t>(rec.size(), 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            A->d_bruns = nullptr;
+            return fail(KLE_ERR_MEM, "out of device memory for the brick runs");
+        }
+        KLE_TRY(h2d(A->d_bruns, rec.data(), sizeof(int) * rec.size()));
+        A->brick_run_cap = G;
+        A->brick_run_stride = rs;
+        A->brick_runs = (int64_t)bp->runs.size();
+        A->brick_run_units = bp->run_units;
+        A->brick_run_items = bp->run_items;
+        A->brick_run_item_loads = bp->run_item_loads;
+    }
     {
         // the gather's runs (kle_sym.hip gsym_gather, the graph kernels'
         // gather): per 64-row slice of [owned | upper ghost planes] in lattice
@@ -1232,7 +1389,7 @@ void brick_pack_desc(const void *plan, const std::vector<int> &srow, std::vector
 
 void brick_drop(kle_mat *A)
 {
-    for (void *q : {A->d_bdesc, (void *)A->d_browd})
+    for (void *q : {A->d_bdesc, (void *)A->d_browd, (void *)A->d_bruns})
         if (q) (void)hipFree(q);
     brick_forget(A);
 }
@@ -1241,6 +1398,9 @@ void brick_forget(kle_mat *A)
 {
     A->d_bdesc = nullptr;
     A->d_browd = nullptr;
+    A->d_bruns = nullptr;
+    A->brick_run_cap = A->brick_run_stride = 0;
+    A->brick_runs = A->brick_run_units = A->brick_run_items = A->brick_run_item_loads = 0;
     A->nbricks = 0;
     A->brick_gparts = 0;
     A->brick_dims[0] = A->brick_dims[1] = A->brick_dims[2] = 0;
@@ -1259,10 +1419,28 @@ void brick_forget(kle_mat *A)
 // array (its loads cached unless spmv_brick_dedup_nt); dot: (A x, x) shares
 using BrickKern = void (*)(int, int, int, int, int, int, const BrickDesc *, const int2 *, const double *, const double *,
                            double *, double *, double *, const int *KLE_PROBE_PARAM);
+// the product takes runs (G of the kernel): built for this matrix, and for the cap the kernel is compiled for
+static bool brick_uses_runs(const kle_mat *A)
+{
+#ifdef KLE_PROBE_BUILD
+    if (g_tune.spmv_sym_probe & 256) return false;  // (timing probe 256: unit by unit, as without the runs)
+#endif
+    return A->brick_dedup && !A->brick_compact && A->d_bruns && A->brick_run_cap == BRICK_RUN_G;
+}
+// (the kernel's row table and its stride: the runs' records where it takes runs)
+static const int2 *brick_rows_of(const kle_mat *A, bool runs)
+{
+    return reinterpret_cast<const int2 *>(runs ? A->d_bruns : A->d_browd);
+}
 template <bool DOT>
 static BrickKern brick_kernel_of(const kle_mat *A)
 {
     if (A->brick_dedup) {
+        if constexpr (!DOT)  // (runs of same-class units: the full layout, no DOT)
+            if (brick_uses_runs(A))
+                return g_tune.spmv_brick_dedup_nt
+                           ? k_nb_spmv_sym_brick<BRICK_WV, true, false, false, true, true, BRICK_RUN_G>
+                           : k_nb_spmv_sym_brick<BRICK_WV, true, false, false, true, false, BRICK_RUN_G>;
         if (g_tune.spmv_brick_dedup_nt)
             return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true, true, true>
                                     : k_nb_spmv_sym_brick<BRICK_WV, true, DOT, false, true, true>;
@@ -1278,13 +1456,12 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
     const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
     const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
     const BrickDesc *bd = reinterpret_cast<const BrickDesc *>(A->d_bdesc);
-    auto go = [&](auto kern, int slot, int wv) {
-        (void)slot;
+    auto go = [&](auto kern, bool runs, int wv) {
         dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * wv), (size_t)A->brick_lds, c->stream,
-                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp, A->brick_rstride, bd,
-                           reinterpret_cast<const int2 *>(A->d_browd), A->d_sval, x->base, A->d_sws, y->d,
-                           dpart, istate KLE_PROBE_ARG);
+                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
+                           runs ? A->brick_run_stride : A->brick_rstride, bd, brick_rows_of(A, runs), A->d_sval,
+                           x->base, A->d_sws, y->d, dpart, istate KLE_PROBE_ARG);
     };
     const bool dist = c->nranks > 1 && (A->lo_rank >= 0 || A->hi_rank >= 0);
     // N > 1 (z slabs): the x ghost planes first (every brick's region fill
@@ -1301,7 +1478,7 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
     } else {
         // (a split product's (A x, x): the bricks' shares, DOT; else the gather's)
         const bool dot = split && dpart && !dist;
-        go(dot ? brick_kernel_of<true>(A) : brick_kernel_of<false>(A), 0, BRICK_WV);
+        go(dot ? brick_kernel_of<true>(A) : brick_kernel_of<false>(A), !dot && brick_uses_runs(A), BRICK_WV);
     }
     KLE_HIP(hipGetLastError());
     // the gather (kle_sym.hip gsym_gather): per row its direct sum in y, then
@@ -1340,12 +1517,13 @@ int brick_spmv_local(kle_mat *A, const kle_vec *x, kle_vec *y)
     const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
     if (A->nbricks > 0) {
         const BrickKern kern = brick_kernel_of<false>(A);
+        const bool runs = brick_uses_runs(A);
         dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * BRICK_WV), (size_t)A->brick_lds, c->stream,
-                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp, A->brick_rstride,
-                           reinterpret_cast<const BrickDesc *>(A->d_bdesc),
-                           reinterpret_cast<const int2 *>(A->d_browd), A->d_sval, x->base, A->d_sws, y->d,
-                           nullptr, nullptr KLE_PROBE_ARG);
+                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
+                           runs ? A->brick_run_stride : A->brick_rstride,
+                           reinterpret_cast<const BrickDesc *>(A->d_bdesc), brick_rows_of(A, runs), A->d_sval,
+                           x->base, A->d_sws, y->d, nullptr, nullptr KLE_PROBE_ARG);
         KLE_HIP(hipGetLastError());
     }
     const int64_t ntot = A->nrows + A->ghost_hi / 3;

@@ -17,7 +17,7 @@ namespace kle {
 struct BrickDesc {
     int x0, y0, z0, nx, ny, nz;
     int ox, oy, oz, RX, RY, RZ;
-    int rstart, eb, nr, pad_;
+    int rstart, eb, nr, nrun;  // (nrun: its runs of same-class units, 0 where none are used)
     long long vbase, wsoff;
 };
 static_assert(sizeof(BrickDesc) == 80, "BrickDesc layout");
@@ -110,7 +110,74 @@ struct BrickPlan {
     // streams share one copy, every brick's vbase is 0, and a unit's second
     // row may lie anywhere in the value array
     bool dedup = false;
+    // runs of same-class units (brick_runs_build, kle_brick_plan.cpp; full
+    // layout on a deduplicated array only): run_order lists brick q's units
+    // (indices into its units of rowd, from rstart / 2) class by class; its
+    // runs are runs[run_first[q] .. run_first[q] + bricks[q].nrun), each
+    // brick_run(first position in that order, count <= run_cap); empty: none.
+    // rowd itself keeps its order: the kernels that take units (DOT, whose
+    // lanes' shares of (A x, x) are summed in unit order) see what they saw.
+    int run_cap = 0;
+    std::vector<int> runs, run_order;
+    std::vector<int64_t> run_first;
+    int64_t run_units = 0, run_classes = 0, run_items = 0, run_item_loads = 0;
 };
+// A unit's class: two units of one class run the identical item sequence --
+// same value loads, same lane layout, same s of the shared item -- and differ
+// only in their rows' region indices.  The key: word 0 of row A without its
+// region-index byte, A's value offset, B null or not, B's word 0 likewise and
+// B's value offset.
+#ifndef KLE_BRICK_RUN_G
+#define KLE_BRICK_RUN_G 4  // (2 and 8 were measured slower or no faster: DESIGN 3; -DKLE_BRICK_RUN_G=n rebuilds for another)
+#endif
+constexpr int BRICK_RUN_G = KLE_BRICK_RUN_G;  // units per run the kernel is built for
+struct BrickUnitKey {
+    int a0, a1, b0, b1;
+    bool operator==(const BrickUnitKey &o) const { return a0 == o.a0 && a1 == o.a1 && b0 == o.b0 && b1 == o.b1; }
+    bool operator<(const BrickUnitKey &o) const
+    {
+        return a0 != o.a0 ? a0 < o.a0 : a1 != o.a1 ? a1 < o.a1 : b0 != o.b0 ? b0 < o.b0 : b1 < o.b1;
+    }
+};
+inline BrickUnitKey brick_unit_key(const int *rowd, int64_t unit_row)  // (unit_row: the descriptor index of row A)
+{
+    const int *d = rowd + 2 * unit_row;
+    const int vm = BRICK_ROW_NULL | (BRICK_ROW_NULL - 1);
+    if (d[3] & BRICK_ROW_NULL) return {d[0] & 0xFFFFFF, d[1] & vm, 0, BRICK_ROW_NULL};
+    return {d[0] & 0xFFFFFF, d[1] & vm, d[2] & 0xFFFFFF, d[3] & vm};
+}
+constexpr int BRICK_RUN_SHIFT = 20;  // a run: first unit | count << 20
+inline int brick_run(int first, int count) { return first | count << BRICK_RUN_SHIFT; }
+inline int brick_run_first(int r) { return r & ((1 << BRICK_RUN_SHIFT) - 1); }
+inline int brick_run_count(int r) { return (int)((unsigned)r >> BRICK_RUN_SHIFT); }
+// a run's record on the device (ints): the class's four descriptor words with
+// the region-index bytes cleared, the count, then per unit irA | irB << 16
+constexpr int brick_run_words(int G) { return (5 + G + 3) & ~3; }
+// items a unit streams (A's passes, the shared item, B's full passes)
+inline int brick_unit_items(const int *rowd, int64_t unit_row)
+{
+    auto mu = [&](int dw) {
+        const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
+        return bnx * bny * bnz - ((dw & 15) + bnx * (((dw >> 4) & 15) + bny * ((dw >> 8) & 15)));
+    };
+    const int *d = rowd + 2 * unit_row;
+    const int ma = mu(d[0]);
+    if (d[3] & BRICK_ROW_NULL) return (ma + 63) / 64;
+    return ma / 64 + 1 + mu(d[2]) / 64;
+}
+// Orders each brick's units so that a class is contiguous (heavier classes
+// first: the brick's tail is short; inside a class the units keep their
+// order) and cuts every class into runs of at most G units.  Which rows form a
+// unit, and rowd, are untouched.  Full layout on a deduplicated array only.
+void brick_runs_build(BrickPlan &bp, int G);
+// ... and taken back (no runs: the units one by one, as without them)
+void brick_runs_clear(BrickPlan &bp);
+// Runs are kept where the items whose values are loaded are at most 3/4 of
+// the items.  Per item the run loop saves the loads and the block positions
+// and pays for its unit loop: measured at item_loads / items 0.370 (config 2)
+// the product takes 0.742 of its time, at 0.948 (config 4: bricks about one
+// element large) 1.05 -- linear in between, even at 0.85; 3/4 leaves a margin.
+inline bool brick_runs_pay(int64_t item_loads, int64_t items) { return items > 0 && 4 * item_loads <= 3 * items; }
 // a row's descriptor word 0 with its boundary bits (compact stream)
 KLE_BRICK_HD inline int brick_dw_bits(int srow, int rb)
 {

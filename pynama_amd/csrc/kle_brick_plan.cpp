@@ -644,7 +644,116 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
             if (bp.dedup && D.vbase != 0) return "a deduplicated row's values";
         }
     }
+    // The runs: the kernel takes a run's class from its first unit and only
+    // the region indices from the others, so a unit of another class inside a
+    // run would be a silently wrong product.  Per brick: every run inside the
+    // brick's units, 1 <= count <= run_cap, every unit in exactly one run, all
+    // units of a run of one class.
+    if (!bp.runs.empty() || bp.run_cap) {
+        if (!bp.dedup || !bp.rbits.empty()) return "runs without a deduplicated full layout";
+        if (bp.run_cap < 1 || bp.run_cap >= (1 << (31 - BRICK_RUN_SHIFT))) return "the runs' cap";
+        if (bp.run_first.size() != bp.bricks.size() || bp.run_order.size() != bp.rowd.size() / 4)
+            return "the runs' table";
+        std::vector<char> seen;
+        for (size_t q = 0; q < bp.bricks.size(); ++q) {
+            const BrickDesc &D = bp.bricks[q];
+            const int NU = D.nr / 2;
+            if (NU >= (1 << BRICK_RUN_SHIFT)) return "a brick's units beyond a run's bits";
+            if (D.nrun < 1 || bp.run_first[q] < 0 || bp.run_first[q] + D.nrun > (int64_t)bp.runs.size())
+                return "a brick's runs";
+            seen.assign(NU, 0);
+            for (int r = 0; r < D.nrun; ++r) {
+                const int rv = bp.runs[bp.run_first[q] + r];
+                const int first = brick_run_first(rv), cnt = brick_run_count(rv);
+                if (cnt < 1 || cnt > bp.run_cap) return "a run's count";
+                if (first < 0 || first + cnt > NU) return "a run leaves its brick's units";
+                // (the run's units: those at its positions in the brick's class order)
+                const int *ord = bp.run_order.data() + D.rstart / 2;
+                BrickUnitKey k0{};
+                for (int g = 0; g < cnt; ++g) {
+                    const int u = ord[first + g];
+                    if (u < 0 || u >= NU) return "a run's unit outside its brick";
+                    if (seen[u]) return "a unit in two runs";
+                    seen[u] = 1;
+                    const BrickUnitKey k = brick_unit_key(bp.rowd.data(), (int64_t)D.rstart + 2 * u);
+                    if (g == 0) k0 = k;
+                    else if (!(k == k0)) return "a run's units of different classes";
+                }
+            }
+            for (int u = 0; u < NU; ++u)
+                if (!seen[u]) return "a unit in no run";
+        }
+    } else {
+        for (const BrickDesc &D : bp.bricks)
+            if (D.nrun != 0) return "a brick's runs without a run table";
+    }
     return nullptr;
+}
+
+void brick_runs_clear(BrickPlan &bp)
+{
+    bp.runs.clear();
+    bp.run_order.clear();
+    bp.run_first.clear();
+    bp.run_cap = 0;
+    bp.run_units = bp.run_classes = bp.run_items = bp.run_item_loads = 0;
+    for (BrickDesc &D : bp.bricks) D.nrun = 0;
+}
+
+void brick_runs_build(BrickPlan &bp, int G)
+{
+    bp.runs.clear();
+    bp.run_first.assign(bp.bricks.size(), 0);
+    bp.run_cap = G;
+    bp.run_units = bp.run_classes = bp.run_items = bp.run_item_loads = 0;
+    bp.run_order.assign(bp.rowd.size() / 4, 0);
+    struct Cls {
+        BrickUnitKey key;
+        int items, first;  // (items of one unit; the class's first unit in the brick's order)
+        std::vector<int> units;
+    };
+    std::vector<int> ord;
+    for (size_t q = 0; q < bp.bricks.size(); ++q) {
+        BrickDesc &D = bp.bricks[q];
+        const int NU = D.nr / 2;
+        const int *rd = bp.rowd.data() + 2 * (int64_t)D.rstart;
+        int *oq = bp.run_order.data() + D.rstart / 2;
+        // classes by key (sorted unit indices: equal keys adjacent, ascending units inside)
+        ord.resize(NU);
+        for (int u = 0; u < NU; ++u) ord[u] = u;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+            return brick_unit_key(rd, 2 * (int64_t)a) < brick_unit_key(rd, 2 * (int64_t)b);
+        });
+        std::vector<Cls> cls;
+        for (int k = 0; k < NU; ++k) {
+            const BrickUnitKey key = brick_unit_key(rd, 2 * (int64_t)ord[k]);
+            if (cls.empty() || !(cls.back().key == key))
+                cls.push_back({key, brick_unit_items(rd, 2 * (int64_t)ord[k]), ord[k], {}});
+            cls.back().units.push_back(ord[k]);
+        }
+        // heavier runs first: by the items a full run of the class streams,
+        // then by the class's first unit (the same order on every run)
+        std::stable_sort(cls.begin(), cls.end(), [&](const Cls &a, const Cls &b) {
+            const int64_t wa = (int64_t)a.items * std::min<int64_t>(G, (int64_t)a.units.size());
+            const int64_t wb = (int64_t)b.items * std::min<int64_t>(G, (int64_t)b.units.size());
+            return wa != wb ? wa > wb : a.first < b.first;
+        });
+        bp.run_first[q] = (int64_t)bp.runs.size();
+        int pos = 0;
+        for (const Cls &c : cls) {
+            const int m = (int)c.units.size();
+            for (int k = 0; k < m; ++k) oq[pos + k] = c.units[k];
+            for (int k = 0; k < m; k += G) {
+                bp.runs.push_back(brick_run(pos + k, std::min(G, m - k)));
+                bp.run_item_loads += c.items;
+            }
+            bp.run_items += (int64_t)c.items * m;
+            pos += m;
+        }
+        D.nrun = (int)(bp.runs.size() - bp.run_first[q]);
+        bp.run_units += NU;
+        bp.run_classes += (int64_t)cls.size();
+    }
 }
 
 }  // namespace kle
@@ -892,6 +1001,87 @@ extern "C" int kle_brick_plan_box_shared(int Lx, int Ly, int Lz, int p, int diri
     out[0] = rows;
     out[1] = kept;
     out[2] = total;
+    if (const char *bad = brick_validate(bp, Lx, Ly, Lz, total, (int64_t)bp.lds))
+        return fail(KLE_ERR_SUP, "brick plan: %s", bad);
+    return 0;
+}
+
+// Diagnostic (host only): the plan of an Lx x Ly x Lz box lattice under the
+// forced split `split` (spmv_brick_split; 0: planned), its value offsets
+// rewritten by packed box as in kle_brick_plan_box_shared, then the runs of at
+// most G same-class units (brick_runs_build) as the device path builds them,
+// checked by brick_validate.  corrupt 1 first swaps the first unit of the
+// first brick's first run with the first unit of a run of another class (the
+// validator must refuse: KLE_ERR_SUP); 2 lengthens the first run by one unit.
+// out[0] units, [1] classes (summed over the bricks), [2] runs, [3] items,
+// [4] items whose values are loaded, [5] the largest run.
+extern "C" int kle_brick_plan_box_runs(int Lx, int Ly, int Lz, int p, int dirichlet, int ncu, int split, int G,
+                                       int corrupt, long long *out)
+{
+    using namespace kle;
+    KLE_ARG(Lx >= 1 && Ly >= 1 && Lz >= 1 && p >= 1 && p <= 7 && ncu >= 1 && split >= 0 && G >= 1 && G <= 64 &&
+                corrupt >= 0 && corrupt <= 2 && out,
+            "bad arg");
+    const int64_t n = (int64_t)Lx * Ly * Lz;
+    std::vector<int> cnt, srow;
+    (void)box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
+    BrickPlan bp;
+    bp.singles = g_tune.spmv_brick_singles;
+    bp.pair = g_tune.spmv_brick_pair;
+    const std::string why = brick_plan(Lx, Ly, Lz, 0, ncu, 0, 1, split, cnt, srow, p, bp);
+    if (!why.empty()) return fail(KLE_ERR_SUP, "%s", why.c_str());
+    std::vector<std::pair<int, int64_t>> first;  // (packed box, offset of the row that keeps its values)
+    int64_t cur = 0;
+    for (BrickDesc &D : bp.bricks) {
+        for (int r = 0; r < D.nr; ++r) {
+            const int64_t rr = (int64_t)D.rstart + r;
+            if (brick_row_null(bp.rowd.data(), rr)) continue;
+            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
+            const int k0 = (dw & 15) + ((dw >> 12) & 15) * (((dw >> 4) & 15) + ((dw >> 16) & 15) * ((dw >> 8) & 15));
+            const int64_t mu = ((dw >> 12) & 15) * ((dw >> 16) & 15) * ((dw >> 20) & 15) - k0;
+            int64_t off = -1;
+            for (const auto &f : first)
+                if (f.first == dw) off = f.second;
+            if (off < 0) {
+                off = cur;
+                first.push_back({dw, off});
+                cur += (9 * mu + 15) & ~int64_t(15);
+            }
+            int &vw = bp.rowd[2 * rr + 1];
+            vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(off >> 4);
+        }
+        D.vbase = 0;
+    }
+    bp.dedup = true;
+    const int64_t total = (cur + 9 * (int64_t)bp.srows.size() + 15) & ~int64_t(15);
+    brick_runs_build(bp, G);
+    int big = 0;
+    for (int rv : bp.runs) big = std::max(big, brick_run_count(rv));
+    out[0] = bp.run_units;
+    out[1] = bp.run_classes;
+    out[2] = (long long)bp.runs.size();
+    out[3] = bp.run_items;
+    out[4] = bp.run_item_loads;
+    out[5] = big;
+    if (corrupt == 1 && !bp.bricks.empty()) {
+        const BrickDesc &D = bp.bricks[0];
+        const int *rd = bp.rowd.data() + 2 * (int64_t)D.rstart;
+        int *oq = bp.run_order.data() + D.rstart / 2;
+        // (the second unit of the first run of two or more, against a unit of another class)
+        int u0 = -1, other = -1;
+        for (int r = 0; r < D.nrun && u0 < 0; ++r)
+            if (brick_run_count(bp.runs[bp.run_first[0] + r]) >= 2) u0 = brick_run_first(bp.runs[bp.run_first[0] + r]) + 1;
+        KLE_ARG(u0 >= 0, "the first brick has no run of two units");
+        const BrickUnitKey k0 = brick_unit_key(rd, 2 * (int64_t)oq[u0]);
+        for (int u = 0; u < D.nr / 2 && other < 0; ++u)
+            if (!(brick_unit_key(rd, 2 * (int64_t)oq[u]) == k0)) other = u;
+        KLE_ARG(other >= 0, "the first brick holds one class only");
+        std::swap(oq[u0], oq[other]);
+    }
+    if (corrupt == 2 && !bp.runs.empty()) {
+        int &rv = bp.runs[bp.run_first[0]];
+        rv = brick_run(brick_run_first(rv), brick_run_count(rv) + 1);
+    }
     if (const char *bad = brick_validate(bp, Lx, Ly, Lz, total, (int64_t)bp.lds))
         return fail(KLE_ERR_SUP, "brick plan: %s", bad);
     return 0;

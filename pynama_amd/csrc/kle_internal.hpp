@@ -294,6 +294,10 @@ struct kle_mat {
     int64_t brick_dropped = 0;      // ... this many entries
     int brick_dedup = 0;            // the bricks' rows with bitwise equal streams share one copy (kle_brick.hip brick_dedup)
     int64_t brick_unique_rows = 0, brick_unique_bytes = 0;  // ... the stored rows and their bytes
+    // runs of same-class units (kle_brick.hpp brick_runs_build): a shared row's values loaded once per run
+    int brick_run_cap = 0, brick_run_stride = 0;  // units per run at most (0: no runs); runs per brick in d_bruns
+    int64_t brick_runs = 0, brick_run_units = 0, brick_run_items = 0, brick_run_item_loads = 0;
+    int *d_bruns = nullptr;  // per brick brick_run_stride records of brick_run_words(cap) ints
     void *d_bdesc = nullptr;
     int *d_browd = nullptr;
     int64_t *d_sbp = nullptr;     // per row: its first stored block in d_slid

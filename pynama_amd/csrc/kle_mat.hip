@@ -1604,6 +1604,19 @@ int kle_mat_get_brick_dedup(const kle_mat *A, int *dedup, long long *unique_rows
     return 0;
 }
 
+int kle_mat_get_brick_runs(const kle_mat *A, int *run_cap, long long *runs, long long *units, long long *items,
+                           long long *item_loads)
+{
+    KLE_ARG(A && run_cap && runs && units && items && item_loads, "null arg");
+    const bool on = A->d_sval && A->sym_brick && A->brick_dedup && !A->brick_compact && A->d_bruns && A->brick_run_cap > 0;
+    *run_cap = on ? A->brick_run_cap : 0;
+    *runs = on ? (long long)A->brick_runs : 0;
+    *units = on ? (long long)A->brick_run_units : 0;
+    *items = on ? (long long)A->brick_run_items : 0;
+    *item_loads = on ? (long long)A->brick_run_item_loads : 0;
+    return 0;
+}
+
 int kle_mat_set_symmetric(kle_mat *A, int on)
 {
     KLE_ARG(A, "null matrix");

@@ -597,9 +597,13 @@ class Mat:
         call("kle_mat_get_brick_compact", self._h, C.byref(cp), C.byref(dr))
         dd, ur, ub = C.c_int(), C.c_longlong(), C.c_longlong()
         call("kle_mat_get_brick_dedup", self._h, C.byref(dd), C.byref(ur), C.byref(ub))
+        rc, rr, ru, ri, rl = C.c_int(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        call("kle_mat_get_brick_runs", self._h, C.byref(rc), C.byref(rr), C.byref(ru), C.byref(ri), C.byref(rl))
         return {"bricks": n.value, "dims": list(dims), "region_entries_per_row": ent.value, "model_us": mus.value,
                 "compact": bool(cp.value), "dropped_entries": dr.value,
-                "dedup": bool(dd.value), "unique_rows": ur.value, "unique_bytes": ub.value}
+                "dedup": bool(dd.value), "unique_rows": ur.value, "unique_bytes": ub.value,
+                "dedup_run_cap": rc.value, "dedup_runs": rr.value, "dedup_units": ru.value,
+                "dedup_items": ri.value, "dedup_item_loads": rl.value}
 
     def moveValues(self, shift, fresh=True):
         """Diagnostic: the symmetric storage's values `shift` bytes into a
