@@ -1,4 +1,13 @@
-// kle_brick.hip -- the box symmetric SpMV on bricks (round 5).
+// kle_brick.hip -- the box symmetric SpMV on bricks: one kernel in four
+// variants and their device set-up.  Full: every stored block's nine doubles,
+// each row its own stream.  Compact: the analytic zeros of a box K left out
+// (kle_brick.hpp brick_drop_bits; chosen in kle_sym.hip sym_build_impl where
+// they are all stored as exact zeros).  Dedup: rows with bitwise equal streams
+// share one copy (brick_dedup, kept where it saves half the bytes), over
+// either layout.  Runs: on a deduplicated full layout a wave takes up to
+// BRICK_RUN_G units of one class at once (brick_runs_build, kept where
+// brick_runs_pay).  brick_kernel_of picks the kernel of a matrix; the row
+// descriptors' layout is kle_brick.hpp's, the plan kle_brick_plan.cpp's.
 //
 // Symmetric (SBAIJ-style, upper-triangle) storage of the structured KLE K
 // (kle_mat_set_symmetric = MatSetOption(MAT_SPD); MatFS.buildFS,
@@ -22,8 +31,9 @@
 // gather (kle_sym.hip gsym_gather) adds, per row, the sums of the bricks
 // whose regions hold it in ascending brick order (bitwise reproducible, as
 // the fixed-point sums are order-free): per 64-row slice of the lattice, each
-// brick region's stretch of one lattice line is one run of consecutive sums.  Inside a brick the waves take rows from
-// an LDS counter, so the brick's end is one row long, not one wave's share.
+// brick region's stretch of one lattice line is one run of consecutive sums.
+// Inside a brick the waves take rows from an LDS counter, so the brick's end
+// is one row long, not one wave's share.
 // The value array is laid out brick by brick (rows in brick order, each row's
 // upper tail in the 16-block chunk layout), so every CU streams one
 // contiguous range.
@@ -227,9 +237,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_nb_spmv_sym_brick(int Lx, int Ly
     cint *rdesc = G > 0 ? (cint *)(reinterpret_cast<const int *>(rowd) + (int64_t)b * rstride * RW)
                         : (cint *)(rowd + (int64_t)b * rstride);
     const double *vb = sval + vbase;
-    // a row from its descriptor (kle_brick.hpp): packed box (dbx, dby, dbz,
-    // bnx, bny, bnz: 4 bits each) + the low byte of its region index; value
-    // offset / 16 doubles (23 bits) + the high byte
+    // a row from its descriptor: the layout kle_brick.hpp brick_row_box,
+    // brick_row_ir and brick_row_off define, decoded here in the kernel's own registers
     auto row_setup = [&](int r, int dw, int vw, BRow &R) {
         constexpr int DM = CP ? 7 : 15;
         const int dbx = dw & DM, dby = (dw >> 4) & DM, dbz = (dw >> 8) & DM;
@@ -833,47 +842,43 @@ __global__ __launch_bounds__(256) void k_brick_bound(int Lx, int Ly, int Lz, int
 // ---------------------------------------------------------------------------
 // host side
 
+// the ghost planes below (zo) and above (hp) the owned lattice (z slabs at N > 1)
+struct BrickGhost { int zo, hp; };
+static BrickGhost brick_ghost_planes(const kle_mat *A)
+{
+    const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
+    return {(int)(A->ghost_lo / plane3), (int)(A->ghost_hi / plane3)};
+}
+
 int brick_setup(kle_mat *A, const std::vector<int> &rb, const std::vector<int> &cnt, const std::vector<int> &srow,
                 int P, std::vector<int64_t> &svptr_out, std::string &why, void **plan_out,
                 const std::vector<unsigned char> &rbits)
 {
-    auto *bp = new BrickPlan;
-    bp->rbits = rbits;
-    bp->singles = g_tune.spmv_brick_singles;
-    bp->pair = g_tune.spmv_brick_pair;
-    const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
+    *plan_out = nullptr;
     if (A->ghost_lo + 3 * A->nrows + A->ghost_hi >= (int64_t)1 << 29) {  // (the fill's 32-bit byte offsets)
-        delete bp;
         why = "brick SpMV: 2^29 / 3 ext nodes or more";
-        *plan_out = nullptr;
         return 0;
     }
+    auto bp = std::make_unique<BrickPlan>();
     // k whole rounds of one brick per CU, k from spmv_brick_rounds up to the
     // fewest whose largest region fits the LDS (config 4, p = 6 on one GPU:
     // 4 rounds; one round at p = 4 and for p = 6 z slabs of 8 ranks)
     for (int rounds = std::max(1, g_tune.spmv_brick_rounds); rounds <= BRICK_MAX_ROUNDS; ++rounds) {
+        *bp = brick_plan_inputs(rbits);
         try {  // (no exception may cross the C ABI: a planner failure is a refusal)
-            why = brick_plan((int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2],
-                             (int)(A->ghost_hi / plane3), std::max(1, A->ctx->num_cus), g_tune.spmv_brick_max, rounds,
-                             g_tune.spmv_brick_split, cnt, srow, P, *bp);
+            why = brick_plan((int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], brick_ghost_planes(A).hp,
+                             std::max(1, A->ctx->num_cus), g_tune.spmv_brick_max, rounds, g_tune.spmv_brick_split, cnt,
+                             srow, P, *bp);
         } catch (const std::exception &e) {
             why = std::string("brick planner: ") + e.what();
         }
         if (why.empty() || g_tune.spmv_brick_max > 0 || g_tune.spmv_brick_split > 0 ||
             why.find("fits the LDS") == std::string::npos)
             break;
-        *bp = BrickPlan{};
-        bp->rbits = rbits;
-        bp->singles = g_tune.spmv_brick_singles;
-        bp->pair = g_tune.spmv_brick_pair;
     }
-    if (!why.empty()) {
-        delete bp;
-        *plan_out = nullptr;
-        return 0;
-    }
+    if (!why.empty()) return 0;
     svptr_out = bp->svb;
-    *plan_out = bp;
+    *plan_out = bp.release();
     return 0;
 }
 
@@ -980,15 +985,11 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
         for (int r = 0; r < D.nr; ++r) {
             const int64_t rr = (int64_t)D.rstart + r;
             if (brick_row_null(bp.rowd.data(), rr)) continue;
-            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
-            const int dm = compact ? 7 : 15;
-            const int dbx = dw & dm, dby = (dw >> 4) & dm, dbz = (dw >> 8) & dm;
-            const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
-            const int64_t mu = bnx * bny * bnz - (dbx + bnx * (dby + bny * dbz));
-            const int64_t len = compact ? brick_row_doubles(dw) : 9 * mu;
+            const int dw = brick_row_word(bp.rowd[2 * rr]);
+            const int64_t len = compact ? brick_row_doubles(dw) : 9 * (int64_t)brick_row_box(dw, false).mu();
             const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), rr), Lx, Ly);
             if (i < 0 || i >= n || len < 1) return 0;  // (brick_validate names what is wrong)
-            const int64_t v0 = D.vbase + (int64_t)(bp.rowd[2 * rr + 1] & (BRICK_ROW_NULL - 1)) * 16;
+            const int64_t v0 = D.vbase + brick_row_off(bp.rowd.data(), rr) * 16;
             const int64_t plen = (len + 15) & ~int64_t(15);
             if (v0 != bp.svb[i] || v0 < 0 || v0 + plen > A->snvals) return 0;
             rows.push_back({i, rr, (int)len, (int)plen});
@@ -1002,40 +1003,29 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
         hlen[r] = rows[r].len;
         hplen[r] = rows[r].plen;
     }
-    int64_t *dstart = nullptr, *ddst = nullptr;
-    int *dlen = nullptr, *dplen = nullptr, *drep = nullptr, *ddiff = nullptr;
-    unsigned long long *dh = nullptr;
-    struct DevFree {  // (freed on every way out)
-        void *&p;
-        ~DevFree()
-        {
-            if (p) (void)hipFree(p);
-        }
-    };
-    DevFree f0{(void *&)dstart}, f1{(void *&)ddst}, f2{(void *&)dlen}, f3{(void *&)dplen}, f4{(void *&)drep},
-        f5{(void *&)ddiff}, f6{(void *&)dh};
-    if (hipMalloc(&dstart, sizeof(int64_t) * nr) != hipSuccess || hipMalloc(&ddst, sizeof(int64_t) * nr) != hipSuccess ||
-        hipMalloc(&dlen, sizeof(int) * nr) != hipSuccess || hipMalloc(&dplen, sizeof(int) * nr) != hipSuccess ||
-        hipMalloc(&drep, sizeof(int) * nr) != hipSuccess || hipMalloc(&ddiff, sizeof(int) * nr) != hipSuccess ||
-        hipMalloc(&dh, sizeof(unsigned long long) * 2 * nr) != hipSuccess) {
+    DevTmp<int64_t> dstart, ddst;  // (freed on every way out)
+    DevTmp<int> dlen, dplen, drep, ddiff;
+    DevTmp<unsigned long long> dh;
+    if (!dstart.alloc(nr) || !ddst.alloc(nr) || !dlen.alloc(nr) || !dplen.alloc(nr) || !drep.alloc(nr) ||
+        !ddiff.alloc(nr) || !dh.alloc(2 * nr)) {
         (void)hipGetLastError();
         return 0;
     }
     const dim3 grid((unsigned)((nr + 3) / 4));
-    KLE_TRY(h2d(dstart, hstart.data(), sizeof(int64_t) * nr));
-    KLE_TRY(h2d(dlen, hlen.data(), sizeof(int) * nr));
-    KLE_TRY(h2d(dplen, hplen.data(), sizeof(int) * nr));
+    KLE_TRY(h2d(dstart.p, hstart.data(), sizeof(int64_t) * nr));
+    KLE_TRY(h2d(dlen.p, hlen.data(), sizeof(int) * nr));
+    KLE_TRY(h2d(dplen.p, hplen.data(), sizeof(int) * nr));
     // 1. hash; equal keys (length, hash) grouped on the host, the smallest
     // natural index first.  A row's box and its role in its unit are not part
     // of the key: each row is read through its own descriptor, only the place
     // of its values is shared, so equal bytes are all the sharing needs (a
     // unit's second row of the compact stream, whose last partial pass comes
     // first, has other bytes than the same row as a first one)
-    hipLaunchKernelGGL(k_brick_row_hash, grid, dim3(256), 0, c->stream, nr, dstart, dlen, A->d_sval, dh);
+    hipLaunchKernelGGL(k_brick_row_hash, grid, dim3(256), 0, c->stream, nr, dstart.p, dlen.p, A->d_sval, dh.p);
     KLE_HIP(hipGetLastError());
     std::vector<unsigned long long> hh(2 * nr);
     KLE_HIP(hipStreamSynchronize(c->stream));
-    KLE_HIP(hipMemcpy(hh.data(), dh, sizeof(unsigned long long) * 2 * nr, hipMemcpyDeviceToHost));
+    KLE_HIP(hipMemcpy(hh.data(), dh.p, sizeof(unsigned long long) * 2 * nr, hipMemcpyDeviceToHost));
     std::vector<int> ord(nr), rep(nr);
     for (int64_t r = 0; r < nr; ++r) ord[r] = (int)r;
     auto key_less = [&](int a, int b) {
@@ -1055,13 +1045,13 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
         rep[ord[k]] = ord[g];
     }
     // 2. the comparison decides: a row that differs anywhere keeps its own storage
-    KLE_TRY(h2d(drep, rep.data(), sizeof(int) * nr));
-    KLE_HIP(hipMemsetAsync(ddiff, 0, sizeof(int) * nr, c->stream));
-    hipLaunchKernelGGL(k_brick_row_cmp, grid, dim3(256), 0, c->stream, nr, dstart, dlen, drep, A->d_sval, ddiff);
+    KLE_TRY(h2d(drep.p, rep.data(), sizeof(int) * nr));
+    KLE_HIP(hipMemsetAsync(ddiff.p, 0, sizeof(int) * nr, c->stream));
+    hipLaunchKernelGGL(k_brick_row_cmp, grid, dim3(256), 0, c->stream, nr, dstart.p, dlen.p, drep.p, A->d_sval, ddiff.p);
     KLE_HIP(hipGetLastError());
     std::vector<int> diff(nr);
     KLE_HIP(hipStreamSynchronize(c->stream));
-    KLE_HIP(hipMemcpy(diff.data(), ddiff, sizeof(int) * nr, hipMemcpyDeviceToHost));
+    KLE_HIP(hipMemcpy(diff.data(), ddiff.p, sizeof(int) * nr, hipMemcpyDeviceToHost));
     // 3. the unique array: the kept rows in brick order, each aligned to 16
     // doubles, then the one-block rows' values (9 doubles each) as before
     std::vector<int64_t> dst(nr, -1);
@@ -1090,24 +1080,17 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
         A->sval_cap = old_cap;
         return 0;
     }
-    double *nv = A->d_sval;
     // (until the copy is done the matrix keeps its full stream: an error
     // return frees exactly one of the two arrays)
+    DevTmp<double> nv(A->d_sval);
     A->d_sval = old;
     A->sval_raw = old_raw == (void *)old ? nullptr : old_raw;
-    struct NewFree {
-        double *&p;
-        ~NewFree()
-        {
-            if (p) (void)hipFree(p);
-        }
-    } fnv{nv};
-    KLE_TRY(h2d(ddst, dst.data(), sizeof(int64_t) * nr));
-    KLE_HIP(hipMemsetAsync(nv, 0, sizeof(double) * std::max<int64_t>(total, 1), c->stream));
-    hipLaunchKernelGGL(k_brick_row_copy, grid, dim3(256), 0, c->stream, nr, dstart, dplen, ddst, old, nv);
+    KLE_TRY(h2d(ddst.p, dst.data(), sizeof(int64_t) * nr));
+    KLE_HIP(hipMemsetAsync(nv.p, 0, sizeof(double) * std::max<int64_t>(total, 1), c->stream));
+    hipLaunchKernelGGL(k_brick_row_copy, grid, dim3(256), 0, c->stream, nr, dstart.p, dplen.p, ddst.p, old, nv.p);
     KLE_HIP(hipGetLastError());
     if (ns)
-        KLE_HIP(hipMemcpyAsync(nv + s_new, old + s_old, sizeof(double) * 9 * ns, hipMemcpyDeviceToDevice, c->stream));
+        KLE_HIP(hipMemcpyAsync(nv.p + s_new, old + s_old, sizeof(double) * 9 * ns, hipMemcpyDeviceToDevice, c->stream));
     // the tables: every row's place in the unique array
     std::vector<int64_t> svb(bp.svb);
     for (int64_t r = 0; r < nr; ++r) svb[rows[r].i] = dst[rep[r]];
@@ -1116,16 +1099,12 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
     KLE_TRY(h2d(A->d_svptr, svb.data(), sizeof(int64_t) * (n + 1)));
     KLE_HIP(hipStreamSynchronize(c->stream));
     (void)hipFree(old_raw);
-    A->d_sval = nv;
-    nv = nullptr;
+    A->d_sval = nv.release();
     A->sval_raw = nullptr;
     A->sval_cap = 0;
     A->snvals = total;
     bp.svb.swap(svb);
-    for (int64_t r = 0; r < nr; ++r) {
-        int &vw = bp.rowd[2 * rows[r].rr + 1];
-        vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(dst[rep[r]] >> 4);
-    }
+    for (int64_t r = 0; r < nr; ++r) brick_row_set_off(bp.rowd.data(), rows[r].rr, dst[rep[r]] >> 4);
     for (BrickDesc &D : bp.bricks) D.vbase = 0;
     bp.dedup = true;
     // units class by class, handed out as runs (the full layout: a unit's
@@ -1144,235 +1123,217 @@ static int brick_dedup(kle_mat *A, BrickPlan &bp)
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// brick_finish's steps, in its order
+
+// the row descriptors, brick q's at row q rstride (the kernel's address needs
+// no load); the rows past a brick's own repeat its last unit (never read:
+// every read is of a unit < nr / 2)
+static int brick_put_rows(kle_mat *A, const BrickPlan &bp, int rstride)
+{
+    const int NB = (int)bp.bricks.size();
+    std::vector<int> pad((size_t)2 * std::max<int64_t>(1, (int64_t)NB * rstride), 0);
+    for (int q = 0; q < NB; ++q) {
+        const BrickDesc &D = bp.bricks[q];
+        int *dst = pad.data() + 2 * (int64_t)q * rstride;
+        std::copy(bp.rowd.begin() + 2 * (int64_t)D.rstart, bp.rowd.begin() + 2 * ((int64_t)D.rstart + D.nr), dst);
+        for (int r = D.nr; r < rstride && D.nr >= 2; ++r) {
+            dst[2 * r] = dst[2 * (D.nr - 2 + (r & 1))];
+            dst[2 * r + 1] = dst[2 * (D.nr - 2 + (r & 1)) + 1];
+        }
+    }
+    KLE_TRY(h2d(A->d_browd, pad.data(), sizeof(int) * pad.size()));
+    A->brick_rstride = rstride;
+    return 0;
+}
+
+// the runs' records, brick q's at q rs (as the row descriptors): the class's
+// four descriptor words without their region-index bytes, the count, each
+// unit's irA | irB << 16 -- all taken from the validated descriptors and
+// runs; the slots past a brick's runs are never read (every read is of a
+// run < nrun)
+static int brick_put_runs(kle_mat *A, const BrickPlan &bp)
+{
+    const int NB = (int)bp.bricks.size(), G = bp.run_cap, RW = brick_run_words(G);
+    const int *rowd = bp.rowd.data();
+    int rs = 1;
+    for (const BrickDesc &D : bp.bricks) rs = std::max(rs, D.nrun);
+    std::vector<int> rec((size_t)NB * rs * RW, 0);
+    for (int q = 0; q < NB; ++q) {
+        const BrickDesc &D = bp.bricks[q];
+        for (int r = 0; r < D.nrun; ++r) {
+            int *o = rec.data() + ((size_t)q * rs + r) * RW;
+            const int rv = bp.runs[bp.run_first[q] + r];
+            const int first = brick_run_first(rv), cnt = brick_run_count(rv);
+            const int *ord = bp.run_order.data() + D.rstart / 2 + first;
+            const int64_t r0 = (int64_t)D.rstart + 2 * ord[0];
+            for (int k = 0; k < 4; ++k) o[k] = brick_row_word(rowd[2 * r0 + k]);
+            o[4] = cnt;
+            for (int g = 0; g < cnt; ++g) {
+                const int64_t ra = (int64_t)D.rstart + 2 * ord[g];
+                const int irb = brick_row_null(rowd, ra + 1) ? 0 : brick_row_ir(rowd, ra + 1);
+                o[5 + g] = brick_row_ir(rowd, ra) | irb << 16;
+            }
+        }
+    }
+    if (hipMalloc(&A->d_bruns, sizeof(int) * std::max<size_t>(rec.size(), 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        A->d_bruns = nullptr;
+        return fail(KLE_ERR_MEM, "out of device memory for the brick runs");
+    }
+    KLE_TRY(h2d(A->d_bruns, rec.data(), sizeof(int) * rec.size()));
+    A->brick_run_cap = G;
+    A->brick_run_stride = rs;
+    A->brick_runs = (int64_t)bp.runs.size();
+    A->brick_run_units = bp.run_units;
+    A->brick_run_items = bp.run_items;
+    A->brick_run_item_loads = bp.run_item_loads;
+    return 0;
+}
+
+// the gather's run lists (kle_brick.hpp brick_gather_runs)
+static int brick_put_gather(kle_mat *A, const BrickPlan &bp)
+{
+    const BrickGhost gp = brick_ghost_planes(A);
+    std::vector<int> runptr, rstart;
+    std::vector<unsigned long long> rmask;
+    if (!brick_gather_runs(bp, A->row_lat[0], A->row_lat[1], A->row_lat[2], gp.zo, gp.hp, runptr, rstart, rmask))
+        return fail(KLE_ERR_SUP, "brick sums beyond 2^31 doubles");
+    const int64_t ns = (int64_t)runptr.size() - 1;
+    if (hipMalloc(&A->d_sgptr, sizeof(int) * (ns + 1)) != hipSuccess ||
+        hipMalloc(&A->d_sgidx, sizeof(int) * rstart.size()) != hipSuccess ||
+        hipMalloc(&A->d_sgmask, sizeof(unsigned long long) * rmask.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KLE_ERR_MEM, "out of device memory for the brick gather runs");
+    }
+    KLE_TRY(h2d(A->d_sgptr, runptr.data(), sizeof(int) * (ns + 1)));
+    KLE_TRY(h2d(A->d_sgidx, rstart.data(), sizeof(int) * rstart.size()));
+    KLE_TRY(h2d(A->d_sgmask, rmask.data(), sizeof(unsigned long long) * rmask.size()));
+    A->brick_gparts = (int)(runptr[ns] / std::max<int64_t>(ns, 1));  // (runs per 64 rows, for the log)
+    A->gather_rps = (int)((runptr[ns] + ns - 1) / std::max<int64_t>(ns, 1));
+    return 0;
+}
+
+// the one-block rows per 64-row slice of the owned rows (the gather forms
+// their B_ii x_i)
+static int brick_put_singles(kle_mat *A, const BrickPlan &bp)
+{
+    const int64_t nso = (A->nrows + 63) / 64;
+    std::vector<unsigned long long> sm(nso, 0ull);
+    for (int64_t i : bp.srows) sm[i >> 6] |= 1ull << (i & 63);
+    if (hipMalloc(&A->d_ssingle, sizeof(unsigned long long) * nso) != hipSuccess) {
+        (void)hipGetLastError();
+        A->d_ssingle = nullptr;
+        return fail(KLE_ERR_MEM, "out of device memory for the brick gather's one-block rows");
+    }
+    return h2d(A->d_ssingle, sm.data(), sizeof(unsigned long long) * nso);
+}
+
+// the bound exponents (k_brick_bound) into the descriptors; dmu: 2 n ints of
+// scratch, freed here
+static int brick_put_bounds(kle_mat *A, BrickPlan &bp, DevTmp<int> &dmu)
+{
+    kle_ctx *c = A->ctx;
+    const int NB = (int)bp.bricks.size();
+    const int64_t n = A->nrows;
+    const bool compact = !bp.rbits.empty();
+    // stored blocks per row (the bound's direct sums) from the row
+    // descriptors | owning brick per row (-1: a one-block row)
+    std::vector<int> hmu(2 * n, 0);
+    int *howner = hmu.data() + n;
+    std::fill(howner, howner + n, -1);
+    for (int64_t i : bp.srows) hmu[i] = 1;
+    for (int q = 0; q < NB; ++q) {
+        const BrickDesc &D = bp.bricks[q];
+        for (int r = 0; r < D.nr; ++r) {
+            const int64_t rr = (int64_t)D.rstart + r;
+            if (brick_row_null(bp.rowd.data(), rr)) continue;
+            const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), rr), A->row_lat[0], A->row_lat[1]);
+            hmu[i] = brick_row_box(bp.rowd[2 * rr], compact).mu();
+            howner[i] = q;
+        }
+    }
+    KLE_TRY(h2d(dmu.p, hmu.data(), sizeof(int) * 2 * n));
+    const BrickGhost gp = brick_ghost_planes(A);
+    if (NB > 0)  // (every row of one block: no brick at all, the gather forms y)
+        hipLaunchKernelGGL(k_brick_bound, dim3((unsigned)NB), dim3(256), 0, c->stream, (int)A->row_lat[0],
+                           (int)A->row_lat[1], (int)A->row_lat[2], gp.zo, gp.hp,
+                           reinterpret_cast<const BrickDesc *>(A->d_bdesc), A->d_rowbox, dmu.p, A->d_svptr, A->d_sval,
+                           A->sym_P, dmu.p + n, A->d_stile_e, A->d_vptr, A->d_rowptr, A->d_rowcnt,
+                           compact ? A->d_val : nullptr);
+    KLE_HIP(hipGetLastError());
+    std::vector<int> eb(NB);
+    KLE_HIP(hipStreamSynchronize(c->stream));
+    KLE_HIP(hipMemcpy(eb.data(), A->d_stile_e, sizeof(int) * NB, hipMemcpyDeviceToHost));
+    (void)hipFree(dmu.release());
+    for (int q = 0; q < NB; ++q) bp.bricks[q].eb = eb[q];
+    return h2d(A->d_bdesc, bp.bricks.data(), sizeof(BrickDesc) * NB);
+}
+
+// what the matrix reports of its bricks
+static int brick_put_stats(kle_mat *A, const BrickPlan &bp)
+{
+    const int NB = (int)bp.bricks.size();
+    const bool compact = !bp.rbits.empty();
+    A->nbricks = NB;
+    std::vector<int> u[3];  // (bricks along each axis: distinct first coordinates)
+    for (const BrickDesc &D : bp.bricks) {
+        u[0].push_back(D.x0);
+        u[1].push_back(D.y0);
+        u[2].push_back(D.z0);
+    }
+    for (int k = 0; k < 3; ++k) {
+        std::sort(u[k].begin(), u[k].end());
+        A->brick_dims[k] = (int)(std::unique(u[k].begin(), u[k].end()) - u[k].begin());
+    }
+    A->brick_model_us = bp.model_us;
+    A->brick_lds = (int)bp.lds;
+    A->sws_entries = bp.ws_entries;
+    A->sym_brick = 1;
+    A->brick_compact = compact;
+    A->brick_dropped = compact ? bp.dropped : 0;
+    if (const char *e = getenv("KLE_TIMING"))
+        if (atoi(e) && NB > 0) {
+            const BrickDesc &D = bp.bricks[0];
+            fprintf(stderr, "[kle brick] %d bricks (first %d x %d x %d rows, region %d x %d x %d), LDS %zu B, "
+                            "region entries %lld (%.2f per row)\n",
+                    NB, D.nx, D.ny, D.nz, D.RX, D.RY, D.RZ, bp.lds, (long long)bp.ws_entries,
+                    (double)bp.ws_entries / A->nrows);
+        }
+    return 0;
+}
+
 // after the values are in place (d_sval, d_svptr in brick layout): the brick
 // tables on the device, the workspace, the bound exponents
 int brick_finish(kle_mat *A, void *plan)
 {
     std::unique_ptr<BrickPlan> bp(reinterpret_cast<BrickPlan *>(plan));
-    kle_ctx *c = A->ctx;
     const int NB = (int)bp->bricks.size();
-    const bool compact = !bp->rbits.empty();
     if (g_tune.spmv_brick_dedup && NB > 0) KLE_TRY(brick_dedup(A, *bp));
     // every address the kernel forms from the tables, checked on the host
     // first (a bad plan is an error, never a launch)
-    {
-        const char *bad = brick_validate(*bp, A->row_lat[0], A->row_lat[1], A->row_lat[2], A->snvals, (int64_t)bp->lds);
-        if (bad) return fail(KLE_ERR_SUP, "brick plan: %s", bad);
-    }
+    if (const char *bad = brick_validate(*bp, A->row_lat[0], A->row_lat[1], A->row_lat[2], A->snvals, (int64_t)bp->lds))
+        return fail(KLE_ERR_SUP, "brick plan: %s", bad);
     int rstride = 0;  // rows per brick in the descriptor table (the most of any brick)
     for (const BrickDesc &D : bp->bricks) rstride = std::max(rstride, D.nr);
     rstride = std::max(2, (rstride + 1) & ~1);  // (whole units of two rows, at least one)
-    const int64_t n = A->nrows;
-    int *dmu = nullptr;
-    std::vector<int> hmu(2 * n, 0);  // stored blocks per row | owning brick per row (-1: a one-block row)
-    int *howner = hmu.data() + n;
-    std::fill(howner, howner + n, -1);
-    for (int64_t i : bp->srows) hmu[i] = 1;
-    bool nomem = hipMalloc(&A->d_bdesc, sizeof(BrickDesc) * std::max(NB, 1)) != hipSuccess ||
-                 hipMalloc(&A->d_browd, sizeof(int) * 2 * std::max<int64_t>(1, (int64_t)NB * rstride)) != hipSuccess ||
-                 (A->ghost_hi && hipMalloc(&A->d_sgsend, sizeof(double) * A->ghost_hi) != hipSuccess) ||
-                 (A->send_lo && hipMalloc(&A->d_sgrecv, sizeof(double) * A->send_lo) != hipSuccess) ||
-                 hipMalloc(&A->d_sws, sizeof(double) * std::max<int64_t>(bp->ws_doubles, 1)) != hipSuccess ||
-                 hipMalloc(&A->d_stile_e, sizeof(int) * std::max(NB, 1)) != hipSuccess ||
-                 hipMalloc(&dmu, sizeof(int) * 2 * n) != hipSuccess;
+    DevTmp<int> dmu;
+    const bool nomem = hipMalloc(&A->d_bdesc, sizeof(BrickDesc) * std::max(NB, 1)) != hipSuccess ||
+                       hipMalloc(&A->d_browd, sizeof(int) * 2 * std::max<int64_t>(1, (int64_t)NB * rstride)) != hipSuccess ||
+                       (A->ghost_hi && hipMalloc(&A->d_sgsend, sizeof(double) * A->ghost_hi) != hipSuccess) ||
+                       (A->send_lo && hipMalloc(&A->d_sgrecv, sizeof(double) * A->send_lo) != hipSuccess) ||
+                       hipMalloc(&A->d_sws, sizeof(double) * std::max<int64_t>(bp->ws_doubles, 1)) != hipSuccess ||
+                       hipMalloc(&A->d_stile_e, sizeof(int) * std::max(NB, 1)) != hipSuccess || !dmu.alloc(2 * A->nrows);
     (void)hipGetLastError();
-    if (nomem) {
-        if (dmu) (void)hipFree(dmu);
-        return fail(KLE_ERR_MEM, "out of device memory for the symmetric SpMV bricks");
-    }
+    if (nomem) return fail(KLE_ERR_MEM, "out of device memory for the symmetric SpMV bricks");
     A->sws_bytes = sizeof(double) * std::max<int64_t>(bp->ws_doubles, 1);
-    // stored blocks per row (the bound's direct sums) from the row descriptors
-    {
-        for (int q = 0; q < NB; ++q) {
-            const BrickDesc &D = bp->bricks[q];
-            for (int r = 0; r < D.nr; ++r) {
-                const int64_t rr = (int64_t)D.rstart + r;
-                if (brick_row_null(bp->rowd.data(), rr)) continue;
-                const int d = bp->rowd[2 * rr];
-                const int dm = compact ? 7 : 15;
-                const int dbx = d & dm, dby = (d >> 4) & dm, dbz = (d >> 8) & dm;
-                const int bnx = (d >> 12) & 15, bny = (d >> 16) & 15, bnz = (d >> 20) & 15;
-                const int64_t i = brick_ir_node(D, brick_row_ir(bp->rowd.data(), rr), A->row_lat[0], A->row_lat[1]);
-                hmu[i] = bnx * bny * bnz - (dbx + bnx * (dby + bny * dbz));
-                howner[i] = q;
-            }
-        }
-    }
     KLE_TRY(h2d(A->d_bdesc, bp->bricks.data(), sizeof(BrickDesc) * NB));
-    {
-        // the row descriptors, brick q's at row q rstride (the kernel's
-        // address needs no load); the rows past a brick's own repeat its
-        // last unit (never read: every read is of a unit < nr / 2)
-        std::vector<int> pad((size_t)2 * std::max<int64_t>(1, (int64_t)NB * rstride), 0);
-        for (int q = 0; q < NB; ++q) {
-            const BrickDesc &D = bp->bricks[q];
-            int *dst = pad.data() + 2 * (int64_t)q * rstride;
-            std::copy(bp->rowd.begin() + 2 * (int64_t)D.rstart, bp->rowd.begin() + 2 * ((int64_t)D.rstart + D.nr), dst);
-            for (int r = D.nr; r < rstride && D.nr >= 2; ++r) {
-                dst[2 * r] = dst[2 * (D.nr - 2 + (r & 1))];
-                dst[2 * r + 1] = dst[2 * (D.nr - 2 + (r & 1)) + 1];
-            }
-        }
-        KLE_TRY(h2d(A->d_browd, pad.data(), sizeof(int) * pad.size()));
-    }
-    A->brick_rstride = rstride;
-    if (!bp->runs.empty()) {
-        // the runs' records, brick q's at q rs (as the row descriptors): the
-        // class's four descriptor words without their region-index bytes, the
-        // count, each unit's irA | irB << 16 -- all taken from the validated
-        // descriptors and runs; the slots past a brick's runs are never read
-        // (every read is of a run < nrun)
-        const int G = bp->run_cap, RW = brick_run_words(G);
-        int rs = 1;
-        for (const BrickDesc &D : bp->bricks) rs = std::max(rs, D.nrun);
-        std::vector<int> rec((size_t)NB * rs * RW, 0);
-        for (int q = 0; q < NB; ++q) {
-            const BrickDesc &D = bp->bricks[q];
-            for (int r = 0; r < D.nrun; ++r) {
-                int *o = rec.data() + ((size_t)q * rs + r) * RW;
-                const int rv = bp->runs[bp->run_first[q] + r];
-                const int first = brick_run_first(rv), cnt = brick_run_count(rv);
-                const int *ord = bp->run_order.data() + D.rstart / 2 + first;
-                const int64_t r0 = (int64_t)D.rstart + 2 * ord[0];
-                for (int k = 0; k < 4; ++k) o[k] = bp->rowd[2 * r0 + k] & 0xFFFFFF;
-                o[4] = cnt;
-                for (int g = 0; g < cnt; ++g) {
-                    const int64_t ra = (int64_t)D.rstart + 2 * ord[g];
-                    const int irb = brick_row_null(bp->rowd.data(), ra + 1) ? 0 : brick_row_ir(bp->rowd.data(), ra + 1);
-                    o[5 + g] = brick_row_ir(bp->rowd.data(), ra) | irb << 16;
-                }
-            }
-        }
-        if (hipMalloc(&A->d_bruns, sizeof(int) * std::max<size_t>(rec.size(), 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            A->d_bruns = nullptr;
-            return fail(KLE_ERR_MEM, "out of device memory for the brick runs");
-        }
-        KLE_TRY(h2d(A->d_bruns, rec.data(), sizeof(int) * rec.size()));
-        A->brick_run_cap = G;
-        A->brick_run_stride = rs;
-        A->brick_runs = (int64_t)bp->runs.size();
-        A->brick_run_units = bp->run_units;
-        A->brick_run_items = bp->run_items;
-        A->brick_run_item_loads = bp->run_item_loads;
-    }
-    {
-        // the gather's runs (kle_sym.hip gsym_gather, the graph kernels'
-        // gather): per 64-row slice of [owned | upper ghost planes] in lattice
-        // order, per real brick in ascending order, each stretch of one
-        // lattice line that the brick's region holds -- consecutive region
-        // entries ([entry][3] at wsoff) -- as (first sum, 64-bit row mask)
-        const int64_t Lx = A->row_lat[0], Ly = A->row_lat[1], Lz = A->row_lat[2];
-        const int64_t p3 = 3 * Lx * Ly;
-        const int64_t zo = A->ghost_lo / p3, hp = A->ghost_hi / p3;
-        const int64_t ntot = n + hp * Lx * Ly, ns = (ntot + 63) / 64;
-        std::vector<std::vector<std::pair<int64_t, unsigned long long>>> sr(ns);
-        for (int q = 0; q < NB; ++q) {
-            const BrickDesc &D = bp->bricks[q];
-            for (int rz = 0; rz < D.RZ; ++rz)
-                for (int ry = 0; ry < D.RY; ++ry) {
-                    const int64_t gy = D.oy + ry, gz = D.oz + rz;
-                    if (gy < 0 || gy >= Ly || gz + zo < 0 || gz >= Lz + hp) continue;
-                    const int64_t x0 = std::max<int64_t>(D.ox, 0), x1 = std::min<int64_t>(D.ox + D.RX, Lx);
-                    if (x1 <= x0) continue;
-                    const int64_t j0 = x0 + Lx * (gy + Ly * gz), j1 = j0 + (x1 - x0);
-                    const int64_t k0 = (x0 - D.ox) + (int64_t)D.RX * (ry + (int64_t)D.RY * rz);
-                    for (int64_t a = j0; a < j1;) {
-                        const int64_t sl = a >> 6, b2 = std::min(j1, (sl + 1) * 64);
-                        unsigned long long m = 0;
-                        for (int64_t jj = a; jj < b2; ++jj) m |= 1ull << (jj & 63);
-                        sr[sl].push_back({D.wsoff + 3 * (k0 + (a - j0)), m});
-                        a = b2;
-                    }
-                }
-        }
-        std::vector<int> runptr(ns + 1, 0), rstart;
-        std::vector<unsigned long long> rmask;
-        for (int64_t sl = 0; sl < ns; ++sl) {
-            runptr[sl + 1] = runptr[sl] + (int)sr[sl].size();
-            for (auto &r : sr[sl]) {
-                if (r.first > INT_MAX) return fail(KLE_ERR_SUP, "brick sums beyond 2^31 doubles");
-                rstart.push_back((int)r.first);
-                rmask.push_back(r.second);
-            }
-        }
-        if (rstart.empty()) {
-            rstart.push_back(0);
-            rmask.push_back(0);
-        }
-        if (hipMalloc(&A->d_sgptr, sizeof(int) * (ns + 1)) != hipSuccess ||
-            hipMalloc(&A->d_sgidx, sizeof(int) * rstart.size()) != hipSuccess ||
-            hipMalloc(&A->d_sgmask, sizeof(unsigned long long) * rmask.size()) != hipSuccess) {
-            (void)hipGetLastError();
-            if (dmu) (void)hipFree(dmu);
-            return fail(KLE_ERR_MEM, "out of device memory for the brick gather runs");
-        }
-        KLE_TRY(h2d(A->d_sgptr, runptr.data(), sizeof(int) * (ns + 1)));
-        KLE_TRY(h2d(A->d_sgidx, rstart.data(), sizeof(int) * rstart.size()));
-        KLE_TRY(h2d(A->d_sgmask, rmask.data(), sizeof(unsigned long long) * rmask.size()));
-        A->brick_gparts = (int)(runptr[ns] / std::max<int64_t>(ns, 1));  // (runs per 64 rows, for the log)
-        A->gather_rps = (int)((runptr[ns] + ns - 1) / std::max<int64_t>(ns, 1));
-    }
-    if (!bp->srows.empty()) {
-        // the one-block rows per 64-row slice of the owned rows (the gather
-        // forms their B_ii x_i)
-        const int64_t nso = (n + 63) / 64;
-        std::vector<unsigned long long> sm(nso, 0ull);
-        for (int64_t i : bp->srows) sm[i >> 6] |= 1ull << (i & 63);
-        if (hipMalloc(&A->d_ssingle, sizeof(unsigned long long) * nso) != hipSuccess) {
-            (void)hipGetLastError();
-            A->d_ssingle = nullptr;
-            if (dmu) (void)hipFree(dmu);
-            return fail(KLE_ERR_MEM, "out of device memory for the brick gather's one-block rows");
-        }
-        KLE_TRY(h2d(A->d_ssingle, sm.data(), sizeof(unsigned long long) * nso));
-    }
-    KLE_TRY(h2d(dmu, hmu.data(), sizeof(int) * 2 * n));
-    const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
-    const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
-    if (NB > 0)  // (every row of one block: no brick at all, the gather forms y)
-        hipLaunchKernelGGL(k_brick_bound, dim3((unsigned)NB), dim3(256), 0, c->stream, (int)A->row_lat[0],
-                           (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
-                           reinterpret_cast<const BrickDesc *>(A->d_bdesc), A->d_rowbox, dmu, A->d_svptr, A->d_sval,
-                           A->sym_P, dmu + n, A->d_stile_e, A->d_vptr, A->d_rowptr, A->d_rowcnt,
-                           compact ? A->d_val : nullptr);
-    KLE_HIP(hipGetLastError());
-    // the exponents into the descriptors
-    std::vector<int> eb(NB);
-    KLE_HIP(hipStreamSynchronize(c->stream));
-    KLE_HIP(hipMemcpy(eb.data(), A->d_stile_e, sizeof(int) * NB, hipMemcpyDeviceToHost));
-    (void)hipFree(dmu);
-    for (int q = 0; q < NB; ++q) bp->bricks[q].eb = eb[q];
-    KLE_TRY(h2d(A->d_bdesc, bp->bricks.data(), sizeof(BrickDesc) * NB));
-    A->nbricks = NB;
-    {
-        // (bricks along each axis: distinct first coordinates)
-        std::vector<int> u[3];
-        for (const BrickDesc &D : bp->bricks) {
-            u[0].push_back(D.x0);
-            u[1].push_back(D.y0);
-            u[2].push_back(D.z0);
-        }
-        for (int k = 0; k < 3; ++k) {
-            std::sort(u[k].begin(), u[k].end());
-            A->brick_dims[k] = (int)(std::unique(u[k].begin(), u[k].end()) - u[k].begin());
-        }
-    }
-    A->brick_model_us = bp->model_us;
-    A->brick_lds = (int)bp->lds;
-    A->sws_entries = bp->ws_entries;
-    A->sym_brick = 1;
-    A->brick_compact = compact;
-    A->brick_dropped = compact ? bp->dropped : 0;
-    if (const char *e = getenv("KLE_TIMING"))
-        if (atoi(e) && NB > 0) {
-            const BrickDesc &D = bp->bricks[0];
-            fprintf(stderr, "[kle brick] %d bricks (first %d x %d x %d rows, region %d x %d x %d), LDS %zu B, "
-                            "region entries %lld (%.2f per row)\n",
-                    NB, D.nx, D.ny, D.nz, D.RX, D.RY, D.RZ, bp->lds, (long long)bp->ws_entries,
-                    (double)bp->ws_entries / n);
-        }
-    return 0;
+    KLE_TRY(brick_put_rows(A, *bp, rstride));
+    if (!bp->runs.empty()) KLE_TRY(brick_put_runs(A, *bp));
+    KLE_TRY(brick_put_gather(A, *bp));
+    if (!bp->srows.empty()) KLE_TRY(brick_put_singles(A, *bp));
+    KLE_TRY(brick_put_bounds(A, *bp, dmu));
+    return brick_put_stats(A, *bp);
 }
 
 void brick_plan_free(void *plan) { delete reinterpret_cast<BrickPlan *>(plan); }
@@ -1427,42 +1388,41 @@ static bool brick_uses_runs(const kle_mat *A)
 #endif
     return A->brick_dedup && !A->brick_compact && A->d_bruns && A->brick_run_cap == BRICK_RUN_G;
 }
-// (the kernel's row table and its stride: the runs' records where it takes runs)
-static const int2 *brick_rows_of(const kle_mat *A, bool runs)
-{
-    return reinterpret_cast<const int2 *>(runs ? A->d_bruns : A->d_browd);
-}
+template <bool DOT, bool CP, bool DD, bool NTL, int G = 0>
+constexpr BrickKern BRICK_KERN = k_nb_spmv_sym_brick<BRICK_WV, true, DOT, CP, DD, NTL, G>;
 template <bool DOT>
 static BrickKern brick_kernel_of(const kle_mat *A)
 {
-    if (A->brick_dedup) {
-        if constexpr (!DOT)  // (runs of same-class units: the full layout, no DOT)
-            if (brick_uses_runs(A))
-                return g_tune.spmv_brick_dedup_nt
-                           ? k_nb_spmv_sym_brick<BRICK_WV, true, false, false, true, true, BRICK_RUN_G>
-                           : k_nb_spmv_sym_brick<BRICK_WV, true, false, false, true, false, BRICK_RUN_G>;
-        if (g_tune.spmv_brick_dedup_nt)
-            return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true, true, true>
-                                    : k_nb_spmv_sym_brick<BRICK_WV, true, DOT, false, true, true>;
-        return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true, true, false>
-                                : k_nb_spmv_sym_brick<BRICK_WV, true, DOT, false, true, false>;
-    }
-    return A->brick_compact ? k_nb_spmv_sym_brick<BRICK_WV, true, DOT, true> : k_nb_spmv_sym_brick<BRICK_WV, true, DOT>;
+    const bool nt = g_tune.spmv_brick_dedup_nt != 0;
+    if constexpr (!DOT)  // (runs of same-class units: the full layout, no DOT)
+        if (brick_uses_runs(A))
+            return nt ? BRICK_KERN<DOT, false, true, true, BRICK_RUN_G> : BRICK_KERN<DOT, false, true, false, BRICK_RUN_G>;
+    // [shared, nontemporal loads | shared, cached loads | every row's own stream][compact | full]
+    // (named in the order the code object has always held them: a reordering moves every kernel in it)
+    static constexpr BrickKern kern[3][2] = {
+        {BRICK_KERN<DOT, true, true, true>, BRICK_KERN<DOT, false, true, true>},
+        {BRICK_KERN<DOT, true, true, false>, BRICK_KERN<DOT, false, true, false>},
+        {BRICK_KERN<DOT, true, false, true>, BRICK_KERN<DOT, false, false, true>},
+    };
+    return kern[!A->brick_dedup ? 2 : nt ? 0 : 1][A->brick_compact ? 0 : 1];
+}
+// the bricks' launch; runs: the kernel takes the runs' records and their stride
+static void brick_launch(kle_mat *A, BrickKern kern, bool runs, const kle_vec *x, kle_vec *y, double *dpart,
+                         const int *istate)
+{
+    kle_ctx *c = A->ctx;
+    const BrickGhost gp = brick_ghost_planes(A);
+    dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * BRICK_WV), (size_t)A->brick_lds, c->stream,
+                       (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], gp.zo, gp.hp,
+                       runs ? A->brick_run_stride : A->brick_rstride, reinterpret_cast<const BrickDesc *>(A->d_bdesc),
+                       reinterpret_cast<const int2 *>(runs ? A->d_bruns : A->d_browd), A->d_sval, x->base, A->d_sws,
+                       y->d, dpart, istate KLE_PROBE_ARG);
 }
 
 int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart, bool split)
 {
     kle_ctx *c = A->ctx;
-    const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
-    const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
-    const BrickDesc *bd = reinterpret_cast<const BrickDesc *>(A->d_bdesc);
-    auto go = [&](auto kern, bool runs, int wv) {
-        dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * wv), (size_t)A->brick_lds, c->stream,
-                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
-                           runs ? A->brick_run_stride : A->brick_rstride, bd, brick_rows_of(A, runs), A->d_sval,
-                           x->base, A->d_sws, y->d, dpart, istate KLE_PROBE_ARG);
-    };
     const bool dist = c->nranks > 1 && (A->lo_rank >= 0 || A->hi_rank >= 0);
     // N > 1 (z slabs): the x ghost planes first (every brick's region fill
     // may read them); after the bricks, the upper ghost nodes' sums go to the
@@ -1478,7 +1438,8 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
     } else {
         // (a split product's (A x, x): the bricks' shares, DOT; else the gather's)
         const bool dot = split && dpart && !dist;
-        go(dot ? brick_kernel_of<true>(A) : brick_kernel_of<false>(A), !dot && brick_uses_runs(A), BRICK_WV);
+        brick_launch(A, dot ? brick_kernel_of<true>(A) : brick_kernel_of<false>(A), !dot && brick_uses_runs(A), x, y, dpart,
+                     istate);
     }
     KLE_HIP(hipGetLastError());
     // the gather (kle_sym.hip gsym_gather): per row its direct sum in y, then
@@ -1513,17 +1474,8 @@ int brick_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, doub
 int brick_spmv_local(kle_mat *A, const kle_vec *x, kle_vec *y)
 {
     kle_ctx *c = A->ctx;
-    const int64_t plane3 = 3 * A->row_lat[0] * A->row_lat[1];
-    const int zo = (int)(A->ghost_lo / plane3), hp = (int)(A->ghost_hi / plane3);
     if (A->nbricks > 0) {
-        const BrickKern kern = brick_kernel_of<false>(A);
-        const bool runs = brick_uses_runs(A);
-        dyn_lds(c, reinterpret_cast<const void *>(kern), (size_t)A->brick_lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)A->nbricks), dim3(64 * BRICK_WV), (size_t)A->brick_lds, c->stream,
-                           (int)A->row_lat[0], (int)A->row_lat[1], (int)A->row_lat[2], zo, hp,
-                           runs ? A->brick_run_stride : A->brick_rstride,
-                           reinterpret_cast<const BrickDesc *>(A->d_bdesc), brick_rows_of(A, runs), A->d_sval,
-                           x->base, A->d_sws, y->d, nullptr, nullptr KLE_PROBE_ARG);
+        brick_launch(A, brick_kernel_of<false>(A), brick_uses_runs(A), x, y, nullptr, nullptr);
         KLE_HIP(hipGetLastError());
     }
     const int64_t ntot = A->nrows + A->ghost_hi / 3;

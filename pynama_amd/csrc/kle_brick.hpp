@@ -22,19 +22,58 @@ struct BrickDesc {
 };
 static_assert(sizeof(BrickDesc) == 80, "BrickDesc layout");
 
-// a row descriptor: word 0 the packed row box (dbx, dby, dbz, bnx, bny, bnz:
-// 4 bits each) + the low byte of its region index; word 1 its value offset
-// / 16 doubles (23 bits), BRICK_ROW_NULL (a unit's absent second row) and the
-// high byte of the region index.  Rows come in units of two (kle_brick_plan.cpp).
-// (The compact value stream, below, puts a boundary bit above each of dbx,
-// dby, dbz.)
+// A row descriptor, two ints.  Word 0: the packed row box -- dbx, dby, dbz (the
+// row's place in its box), bnx, bny, bnz (the box's size), 4 bits each from
+// bit 0 -- and, in its top byte, the low byte of the row's region index.
+// Word 1: the row's value offset / 16 doubles (23 bits), BRICK_ROW_NULL (a
+// unit's absent second row) and, in its top byte, the high byte of the region
+// index.  Rows come in units of two (kle_brick_plan.cpp).  The compact value
+// stream (below) puts a boundary bit above each of dbx, dby, dbz, which are
+// then 3 bits.  The functions from here to brick_row_set_null are the one
+// definition of this layout; every shift is unsigned.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define KLE_BRICK_HD __host__ __device__
+#else
+#define KLE_BRICK_HD
+#endif
 constexpr int BRICK_ROW_NULL = 1 << 23;
+constexpr int BRICK_ROW_OFF = BRICK_ROW_NULL - 1;  // (word 1: the value offset's bits)
+struct BrickRowBox {
+    int dbx, dby, dbz, bnx, bny, bnz;
+    KLE_BRICK_HD int k0() const { return dbx + bnx * (dby + bny * dbz); }  // the row's own (first stored) block
+    KLE_BRICK_HD int mu() const { return bnx * bny * bnz - k0(); }         // its stored blocks
+};
+// the box of a packed box word (kle_sym.hip srow, or word 0 of a descriptor);
+// compact: the word carries the boundary bits
+KLE_BRICK_HD inline BrickRowBox brick_row_box(int dw, bool compact)
+{
+    const unsigned w = (unsigned)dw, dm = compact ? 7u : 15u;
+    return {(int)(w & dm), (int)((w >> 4) & dm), (int)((w >> 8) & dm),
+            (int)((w >> 12) & 15u), (int)((w >> 16) & 15u), (int)((w >> 20) & 15u)};
+}
+// a descriptor word without its region-index byte: the packed box of word 0,
+// the value offset and the null bit of word 1
+KLE_BRICK_HD inline int brick_row_word(int w) { return (int)((unsigned)w & 0xFFFFFFu); }
 inline bool brick_row_null(const int *rowd, int64_t r) { return (rowd[2 * r + 1] & BRICK_ROW_NULL) != 0; }
 // a row descriptor's region index (the low and high bytes of its two words)
 inline int brick_row_ir(const int *rowd, int64_t r)
 {
-    return ((rowd[2 * r] >> 24) & 255) | (((rowd[2 * r + 1] >> 24) & 255) << 8);
+    return (int)(((unsigned)rowd[2 * r] >> 24) | (((unsigned)rowd[2 * r + 1] >> 24) << 8));
 }
+// its value offset in units of 16 doubles, read and rewritten (the null bit
+// and the region byte stay)
+inline int64_t brick_row_off(const int *rowd, int64_t r) { return rowd[2 * r + 1] & BRICK_ROW_OFF; }
+inline void brick_row_set_off(int *rowd, int64_t r, int64_t off16)
+{
+    rowd[2 * r + 1] = (int)(((unsigned)rowd[2 * r + 1] & ~(unsigned)BRICK_ROW_OFF) | (unsigned)off16);
+}
+// a real row (packed box, region index, offset < 2^23) and the null row
+inline void brick_row_set(int *rowd, int64_t r, int dw, int ir, int64_t off16)
+{
+    rowd[2 * r] = (int)((unsigned)brick_row_word(dw) | ((unsigned)(ir & 255) << 24));
+    rowd[2 * r + 1] = (int)((unsigned)off16 | ((unsigned)((ir >> 8) & 255) << 24));
+}
+inline void brick_row_set_null(int *rowd, int64_t r) { rowd[2 * r] = 0, rowd[2 * r + 1] = BRICK_ROW_NULL; }
 // the owned-lattice node of region index ir of brick D
 inline int64_t brick_ir_node(const BrickDesc &D, int ir, int64_t Lx, int64_t Ly)
 {
@@ -52,11 +91,6 @@ inline int64_t brick_ir_node(const BrickDesc &D, int ir, int64_t Lx, int64_t Ly)
 // the pair (0,1), bit 1 (0,2), bit 2 (1,2).  The one place that decides what
 // the stream holds: the planner's sizes, the pack and the kernel's loads all
 // come here.
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define KLE_BRICK_HD __host__ __device__
-#else
-#define KLE_BRICK_HD
-#endif
 KLE_BRICK_HD inline int brick_drop_bits(int dw, int kx, int ky, int kz)
 {
     const int s0 = ((dw >> 3) & 1) & (int)(kx == (dw & 7));
@@ -69,9 +103,8 @@ KLE_BRICK_HD inline int brick_slot_pair(int t) { return t == 1 || t == 3 ? 0 : t
 // doubles a row holds in the compact stream, and how many entries it leaves out
 inline int64_t brick_row_doubles(int dw, int64_t *dropped = nullptr)
 {
-    const int dbx = dw & 7, dby = (dw >> 4) & 7, dbz = (dw >> 8) & 7;
-    const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
-    const int k0 = dbx + bnx * (dby + bny * dbz), m = bnx * bny * bnz;
+    const BrickRowBox b = brick_row_box(dw, true);
+    const int bnx = b.bnx, bny = b.bny, k0 = b.k0(), m = bnx * bny * b.bnz;
     int64_t out = 0;
     for (int k = k0; k < m; ++k) {
         const int kz = k / (bnx * bny), ky = (k - kz * bnx * bny) / bnx, kx = k - kz * bnx * bny - ky * bnx;
@@ -86,9 +119,6 @@ constexpr int BRICK_MAX_ROUNDS = 8;        // bricks per CU the planner goes up 
 constexpr int BRICK_WV = 16;            // waves per brick workgroup (one workgroup per CU)
 constexpr size_t BRICK_LDS_CAP = 163840;  // LDS per CU
 constexpr size_t BRICK_LDS_MIN = 82 * 1024;  // above half the CU's LDS: never two bricks on one CU
-
-// dynamic LDS of a brick: x [3][RN] | sums [3][RN + 64] (64 dummy slots per
-// component take the adds of masked lanes) | wave maxima, row counter
 
 struct BrickPlan {
     std::vector<BrickDesc> bricks;  // the bricks (tail tiles last), in launch order
@@ -142,9 +172,8 @@ struct BrickUnitKey {
 inline BrickUnitKey brick_unit_key(const int *rowd, int64_t unit_row)  // (unit_row: the descriptor index of row A)
 {
     const int *d = rowd + 2 * unit_row;
-    const int vm = BRICK_ROW_NULL | (BRICK_ROW_NULL - 1);
-    if (d[3] & BRICK_ROW_NULL) return {d[0] & 0xFFFFFF, d[1] & vm, 0, BRICK_ROW_NULL};
-    return {d[0] & 0xFFFFFF, d[1] & vm, d[2] & 0xFFFFFF, d[3] & vm};
+    if (brick_row_null(rowd, unit_row + 1)) return {brick_row_word(d[0]), brick_row_word(d[1]), 0, BRICK_ROW_NULL};
+    return {brick_row_word(d[0]), brick_row_word(d[1]), brick_row_word(d[2]), brick_row_word(d[3])};
 }
 constexpr int BRICK_RUN_SHIFT = 20;  // a run: first unit | count << 20
 inline int brick_run(int first, int count) { return first | count << BRICK_RUN_SHIFT; }
@@ -156,14 +185,9 @@ constexpr int brick_run_words(int G) { return (5 + G + 3) & ~3; }
 // items a unit streams (A's passes, the shared item, B's full passes)
 inline int brick_unit_items(const int *rowd, int64_t unit_row)
 {
-    auto mu = [&](int dw) {
-        const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
-        return bnx * bny * bnz - ((dw & 15) + bnx * (((dw >> 4) & 15) + bny * ((dw >> 8) & 15)));
-    };
-    const int *d = rowd + 2 * unit_row;
-    const int ma = mu(d[0]);
-    if (d[3] & BRICK_ROW_NULL) return (ma + 63) / 64;
-    return ma / 64 + 1 + mu(d[2]) / 64;
+    const int ma = brick_row_box(rowd[2 * unit_row], false).mu();
+    if (brick_row_null(rowd, unit_row + 1)) return (ma + 63) / 64;
+    return ma / 64 + 1 + brick_row_box(rowd[2 * unit_row + 2], false).mu() / 64;
 }
 // Orders each brick's units so that a class is contiguous (heavier classes
 // first: the brick's tail is short; inside a class the units keep their
@@ -181,7 +205,7 @@ inline bool brick_runs_pay(int64_t item_loads, int64_t items) { return items > 0
 // a row's descriptor word 0 with its boundary bits (compact stream)
 KLE_BRICK_HD inline int brick_dw_bits(int srow, int rb)
 {
-    return (srow & 0xFFFFFF) | ((rb & 1) << 3) | (((rb >> 1) & 1) << 7) | (((rb >> 2) & 1) << 11);
+    return brick_row_word(srow) | ((rb & 1) << 3) | (((rb >> 1) & 1) << 7) | (((rb >> 2) & 1) << 11);
 }
 
 // the plan's tables checked against every address the brick kernel forms
@@ -208,5 +232,20 @@ constexpr int GB_UCAP = (int)((BRICK_LDS_CAP - 2048) / 48);
 // split counts (0: planned).  "" or why not.
 std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int rounds, int fs, const std::vector<int> &cnt,
                        const std::vector<int> &srow, int P, BrickPlan &bp);
+// a plan with its inputs set: singles and pair from the tuning, rbits as given
+BrickPlan brick_plan_inputs(const std::vector<unsigned char> &rbits = {});
+// (diagnostics) the value offsets as the row dedup rewrites them for a K whose
+// rows with equal packed boxes are equal: the first such row in brick order
+// keeps its values, the others point at them, every brick's vbase is 0
+struct BrickShared {
+    int64_t rows = 0, kept = 0, total = 0, last = -1;  // rows in bricks, rows stored, doubles of the array, the last row
+};
+BrickShared brick_share_by_box(BrickPlan &bp);
+// The gather's run lists (kle_sym.hip gsym_gather): per 64-row slice of
+// [owned | hp upper ghost planes], per brick in ascending order, each stretch
+// of a lattice line in the brick's region as (first sum, 64-bit row mask);
+// zo: lower ghost planes.  False: sums beyond 2^31 doubles.
+bool brick_gather_runs(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t Lz, int64_t zo, int64_t hp,
+                       std::vector<int> &runptr, std::vector<int> &rstart, std::vector<unsigned long long> &rmask);
 
 }  // namespace kle

@@ -72,11 +72,9 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
     double total = 0.0;  // (all rows; KLE_TIMING)
     for (int64_t i = 0; i < n; ++i) {
         const int z = (int)(i / Lxy), y = (int)((i % Lxy) / Lx), x = (int)(i % Lx);
-        const int d = srow[i];
-        const int dbx = d & 15, dby = (d >> 4) & 15, dbz = (d >> 8) & 15;
-        const int bnx = (d >> 12) & 15, bny = (d >> 16) & 15, bnz = (d >> 20) & 15;
-        const int k0 = dbx + bnx * (dby + bny * dbz);
-        mu[i] = cnt[i] - k0;
+        const BrickRowBox b = brick_row_box(srow[i], false);
+        const int dbx = b.dbx, dby = b.dby, dbz = b.dbz, bnx = b.bnx, bny = b.bny, bnz = b.bnz;
+        mu[i] = cnt[i] - b.k0();
         const double wgt = rcost(i);
         wx[x] += wgt;
         wy[y] += wgt;
@@ -553,9 +551,7 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
         for (const auto &u : units)
             for (int64_t i : {u.first, u.second}) {
                 if (i < 0) {  // (no partner: the null descriptor)
-                    bp.rowd[2 * rows] = 0;
-                    bp.rowd[2 * rows + 1] = BRICK_ROW_NULL;
-                    ++rows;
+                    brick_row_set_null(bp.rowd.data(), rows++);
                     continue;
                 }
                 const int z = (int)(i / Lxy), y = (int)((i % Lxy) / Lx), x = (int)(i % Lx);
@@ -563,9 +559,8 @@ std::string brick_plan(int Lx, int Ly, int Lz, int hp, int ncu, int nfix, int ro
                 const int64_t o = voff - D.vbase;
                 if ((o >> 4) >= (1 << 23)) return "brick values beyond 2^27 doubles";
                 const int ir = (x - D.ox) + D.RX * ((y - D.oy) + D.RY * (z - D.oz));
-                const int dw = compact ? brick_dw_bits(srow[i], bp.rbits[i]) : (srow[i] & 0xFFFFFF);
-                bp.rowd[2 * rows] = dw | ((ir & 255) << 24);
-                bp.rowd[2 * rows + 1] = (int)((o >> 4) | ((int64_t)((ir >> 8) & 255) << 24));
+                const int dw = compact ? brick_dw_bits(srow[i], bp.rbits[i]) : brick_row_word(srow[i]);
+                brick_row_set(bp.rowd.data(), rows, dw, ir, o >> 4);
                 if (compact) {
                     bp.second[i] = i == u.second;
                     voff += (brick_row_doubles(dw, &bp.dropped) + 15) & ~int64_t(15);
@@ -617,24 +612,22 @@ const char *brick_validate(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t 
         int64_t a_v0 = 0;
         for (int r = 0; r < D.nr; ++r) {
             const int64_t rr = (int64_t)D.rstart + r;
-            const int dw = bp.rowd[2 * rr], vw = bp.rowd[2 * rr + 1];
-            if (vw & BRICK_ROW_NULL) {
+            const int dw = bp.rowd[2 * rr];
+            if (brick_row_null(bp.rowd.data(), rr)) {
                 if (r % 2 == 0) return "a unit's first row is null";
                 continue;
             }
             const bool compact = !bp.rbits.empty();
-            const int dm = compact ? 7 : 15;  // (compact: the nibbles' top bits are the boundary bits)
-            const int dbx = dw & dm, dby = (dw >> 4) & dm, dbz = (dw >> 8) & dm;
-            const int bnx = (dw >> 12) & 15, bny = (dw >> 16) & 15, bnz = (dw >> 20) & 15;
-            const int k0 = dbx + bnx * (dby + bny * dbz), mu = bnx * bny * bnz - k0;
-            if (dbx >= bnx || dby >= bny || dbz >= bnz || mu < 1) return "a row's box";
+            const BrickRowBox b = brick_row_box(dw, compact);
+            const int mu = b.mu();
+            if (b.dbx >= b.bnx || b.dby >= b.bny || b.dbz >= b.bnz || mu < 1) return "a row's box";
             const int ir = brick_row_ir(bp.rowd.data(), rr);
             if (ir < 0 || ir >= RN) return "a row's region index";
             const int irz = ir / (D.RX * D.RY), irem = ir - irz * D.RX * D.RY, iry = irem / D.RX, irx = irem - iry * D.RX;
             const int64_t gx = D.ox + irx, gy = D.oy + iry, gz = D.oz + irz;
             if (gx < 0 || gx >= Lx || gy < 0 || gy >= Ly || gz < 0 || gz >= Lz) return "a row's lattice node";
-            const int64_t v0 = D.vbase + (int64_t)(vw & (BRICK_ROW_NULL - 1)) * 16;
-            const int64_t v1 = v0 + (compact ? brick_row_doubles(dw & 0xFFFFFF) : 9 * (int64_t)mu);
+            const int64_t v0 = D.vbase + brick_row_off(bp.rowd.data(), rr) * 16;
+            const int64_t v1 = v0 + (compact ? brick_row_doubles(brick_row_word(dw)) : 9 * (int64_t)mu);
             if (v0 < 0 || v1 > nvals) return "a row's values";
             if (r % 2 == 0) a_v0 = v0;
             else if (!bp.dedup && (v0 < a_v0 || v0 - a_v0 > ((int64_t)1 << 26))) return "a unit's second row's values";
@@ -756,6 +749,85 @@ void brick_runs_build(BrickPlan &bp, int G)
     }
 }
 
+BrickPlan brick_plan_inputs(const std::vector<unsigned char> &rbits)
+{
+    BrickPlan bp;
+    bp.rbits = rbits;
+    bp.singles = g_tune.spmv_brick_singles;
+    bp.pair = g_tune.spmv_brick_pair;
+    return bp;
+}
+
+BrickShared brick_share_by_box(BrickPlan &bp)
+{
+    BrickShared s;
+    std::vector<std::pair<int, int64_t>> first;  // (packed box, offset of the row that keeps its values)
+    int64_t cur = 0;
+    for (BrickDesc &D : bp.bricks) {
+        for (int r = 0; r < D.nr; ++r) {
+            const int64_t rr = (int64_t)D.rstart + r;
+            if (brick_row_null(bp.rowd.data(), rr)) continue;
+            const int dw = brick_row_word(bp.rowd[2 * rr]);
+            int64_t off = -1;
+            for (const auto &f : first)
+                if (f.first == dw) off = f.second;
+            if (off < 0) {
+                off = cur;
+                first.push_back({dw, off});
+                cur += (9 * (int64_t)brick_row_box(dw, false).mu() + 15) & ~int64_t(15);
+                ++s.kept;
+            }
+            brick_row_set_off(bp.rowd.data(), rr, off >> 4);
+            s.last = rr;
+            ++s.rows;
+        }
+        D.vbase = 0;
+    }
+    bp.dedup = true;
+    s.total = (cur + 9 * (int64_t)bp.srows.size() + 15) & ~int64_t(15);
+    return s;
+}
+
+bool brick_gather_runs(const BrickPlan &bp, int64_t Lx, int64_t Ly, int64_t Lz, int64_t zo, int64_t hp,
+                       std::vector<int> &runptr, std::vector<int> &rstart, std::vector<unsigned long long> &rmask)
+{
+    const int64_t ntot = Lx * Ly * (Lz + hp), ns = (ntot + 63) / 64;
+    std::vector<std::vector<std::pair<int64_t, unsigned long long>>> sr(ns);
+    for (const BrickDesc &D : bp.bricks)
+        for (int rz = 0; rz < D.RZ; ++rz)
+            for (int ry = 0; ry < D.RY; ++ry) {
+                const int64_t gy = D.oy + ry, gz = D.oz + rz;
+                if (gy < 0 || gy >= Ly || gz + zo < 0 || gz >= Lz + hp) continue;
+                const int64_t x0 = std::max<int64_t>(D.ox, 0), x1 = std::min<int64_t>(D.ox + D.RX, Lx);
+                if (x1 <= x0) continue;
+                const int64_t j0 = x0 + Lx * (gy + Ly * gz), j1 = j0 + (x1 - x0);
+                const int64_t k0 = (x0 - D.ox) + (int64_t)D.RX * (ry + (int64_t)D.RY * rz);
+                for (int64_t a = j0; a < j1;) {
+                    const int64_t sl = a >> 6, b2 = std::min(j1, (sl + 1) * 64);
+                    unsigned long long m = 0;
+                    for (int64_t jj = a; jj < b2; ++jj) m |= 1ull << (jj & 63);
+                    sr[sl].push_back({D.wsoff + 3 * (k0 + (a - j0)), m});
+                    a = b2;
+                }
+            }
+    runptr.assign(ns + 1, 0);
+    rstart.clear();
+    rmask.clear();
+    for (int64_t sl = 0; sl < ns; ++sl) {
+        runptr[sl + 1] = runptr[sl] + (int)sr[sl].size();
+        for (auto &r : sr[sl]) {
+            if (r.first > INT_MAX) return false;
+            rstart.push_back((int)r.first);
+            rmask.push_back(r.second);
+        }
+    }
+    if (rstart.empty()) {
+        rstart.push_back(0);
+        rmask.push_back(0);
+    }
+    return true;
+}
+
 }  // namespace kle
 
 // the node-block pattern of MatFS.buildFS on an Lx x Ly x Lz box lattice of
@@ -817,9 +889,7 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
     const int64_t n = (int64_t)Lx * Ly * Lz;
     std::vector<int> cnt, srow;
     const int64_t blocks = box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
-    BrickPlan bp;
-    bp.singles = g_tune.spmv_brick_singles;
-    bp.pair = g_tune.spmv_brick_pair;
+    BrickPlan bp = brick_plan_inputs();
     const std::string why = brick_plan(Lx, Ly, Lz, 0, ncu, 0, rounds, split, cnt, srow, p, bp);
     if (!why.empty()) return fail(KLE_ERR_SUP, "%s", why.c_str());
     const int NB = (int)bp.bricks.size();
@@ -842,16 +912,16 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
             }
     }
     double tot = 0.0, mx = 0.0;
-    // a brick's weight: its rows' costs (the rows from its descriptors)
+    // a real row's stored blocks by the pattern (the row from its descriptor)
+    auto row_mu = [&](const BrickDesc &D, int r) {
+        const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), (int64_t)D.rstart + r), Lx, Ly);
+        return cnt[i] - brick_row_box(srow[i], false).k0();
+    };
+    // a brick's weight: its rows' costs
     auto weight = [&](const BrickDesc &D) {
         double w = 0.0;
-        for (int r = 0; r < D.nr; ++r) {
-            if (brick_row_null(bp.rowd.data(), (int64_t)D.rstart + r)) continue;
-            const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), (int64_t)D.rstart + r), Lx, Ly);
-            const int d = srow[i];
-            const int k0 = (d & 15) + ((d >> 12) & 15) * (((d >> 4) & 15) + ((d >> 16) & 15) * ((d >> 8) & 15));
-            w += row_cost(cnt[i] - k0);
-        }
+        for (int r = 0; r < D.nr; ++r)
+            if (!brick_row_null(bp.rowd.data(), (int64_t)D.rstart + r)) w += row_cost(row_mu(D, r));
         return w;
     };
     for (const BrickDesc &D : bp.bricks) {
@@ -883,37 +953,27 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
     // the items the bricks stream (a unit of two rows: their full passes and
     // one shared item) and the share of their lanes that carry a block
     {
-        auto rmu = [&](int64_t r) {
-            const int d = bp.rowd[2 * r];
-            const int dbx = d & 15, dby = (d >> 4) & 15, dbz = (d >> 8) & 15;
-            const int bnx = (d >> 12) & 15, bny = (d >> 16) & 15, bnz = (d >> 20) & 15;
-            return bnx * bny * bnz - (dbx + bnx * (dby + bny * dbz));
-        };
+        auto rmu = [&](int64_t r) { return brick_row_box(bp.rowd[2 * r], false).mu(); };
         int64_t items = 0, blocks_b = 0;
         for (const BrickDesc &D : bp.bricks)
             for (int u = 0; u < D.nr / 2; ++u) {
                 const int64_t ra = (int64_t)D.rstart + 2 * u, rb = ra + 1;
                 const int ma = rmu(ra);
                 blocks_b += ma;
-                if (brick_row_null(bp.rowd.data(), rb)) {
-                    items += (ma + 63) / 64;
-                } else {
+                if (!brick_row_null(bp.rowd.data(), rb)) {
                     const int mb = rmu(rb);
                     blocks_b += mb;
                     if (ma % 64 == 0 || mb % 64 == 0 || ma % 64 + mb % 64 > 64)
                         return fail(KLE_ERR_SUP, "brick plan: a unit whose tails do not share an item");
-                    items += ma / 64 + mb / 64 + 1;
                 }
+                items += brick_unit_items(bp.rowd.data(), ra);
             }
         stats[4] = (double)items;
         stats[5] = items ? (double)blocks_b / (64.0 * (double)items) : 0.0;
     }
-    {
-        // (the tables checked as brick_finish checks them on the device path;
-        // the values: the plan's own layout)
-        if (const char *bad = brick_validate(bp, Lx, Ly, Lz, bp.svb[n], (int64_t)bp.lds))
-            return fail(KLE_ERR_SUP, "brick plan: %s", bad);
-    }
+    // (the tables checked as brick_finish checks them; the values: the plan's own layout)
+    if (const char *bad = brick_validate(bp, Lx, Ly, Lz, bp.svb[n], (int64_t)bp.lds))
+        return fail(KLE_ERR_SUP, "brick plan: %s", bad);
     if (getenv("KLE_BRICK_DEBUG"))
         for (const BrickDesc &D : bp.bricks) {
             // (stored blocks, rows of one stored block, rows past one 64-block pass)
@@ -921,10 +981,7 @@ extern "C" int kle_brick_plan_box(int Lx, int Ly, int Lz, int p, int dirichlet, 
             int one = 0, two = 0;
             for (int r = 0; r < D.nr; ++r) {
                 if (brick_row_null(bp.rowd.data(), (int64_t)D.rstart + r)) continue;
-                const int64_t i = brick_ir_node(D, brick_row_ir(bp.rowd.data(), (int64_t)D.rstart + r), Lx, Ly);
-                const int d = srow[i];
-                const int k0 = (d & 15) + ((d >> 12) & 15) * (((d >> 4) & 15) + ((d >> 16) & 15) * ((d >> 8) & 15));
-                const int mu = cnt[i] - k0;
+                const int mu = row_mu(D, r);
                 sb += mu;
                 one += mu == 1;
                 two += mu > 64;
@@ -954,52 +1011,24 @@ extern "C" int kle_brick_plan_box_shared(int Lx, int Ly, int Lz, int p, int diri
     const int64_t n = (int64_t)Lx * Ly * Lz;
     std::vector<int> cnt, srow;
     (void)box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
-    BrickPlan bp;
-    bp.singles = g_tune.spmv_brick_singles;
-    bp.pair = g_tune.spmv_brick_pair;
+    BrickPlan bp = brick_plan_inputs();
     const std::string why = brick_plan(Lx, Ly, Lz, 0, ncu, 0, 1, 0, cnt, srow, p, bp);
     if (!why.empty()) return fail(KLE_ERR_SUP, "%s", why.c_str());
     if (const char *bad = brick_validate(bp, Lx, Ly, Lz, bp.svb[n], (int64_t)bp.lds))
         return fail(KLE_ERR_SUP, "brick plan: %s", bad);
-    std::vector<std::pair<int, int64_t>> first;  // (packed box, offset of the row that keeps its values)
-    int64_t cur = 0, rows = 0, kept = 0, last = -1;
-    for (BrickDesc &D : bp.bricks) {
-        for (int r = 0; r < D.nr; ++r) {
-            const int64_t rr = (int64_t)D.rstart + r;
-            if (brick_row_null(bp.rowd.data(), rr)) continue;
-            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
-            const int k0 = (dw & 15) + ((dw >> 12) & 15) * (((dw >> 4) & 15) + ((dw >> 16) & 15) * ((dw >> 8) & 15));
-            const int64_t mu = ((dw >> 12) & 15) * ((dw >> 16) & 15) * ((dw >> 20) & 15) - k0;
-            int64_t off = -1;
-            for (const auto &f : first)
-                if (f.first == dw) off = f.second;
-            if (off < 0) {
-                off = cur;
-                first.push_back({dw, off});
-                cur += (9 * mu + 15) & ~int64_t(15);
-                ++kept;
-            }
-            int &vw = bp.rowd[2 * rr + 1];
-            vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(off >> 4);
-            last = rr;
-            ++rows;
-        }
-        D.vbase = 0;
-    }
-    bp.dedup = true;
-    int64_t total = (cur + 9 * (int64_t)bp.srows.size() + 15) & ~int64_t(15);
+    const BrickShared s = brick_share_by_box(bp);
+    int64_t total = s.total;
     if (shift < 0 && !bp.bricks.empty()) {
         bp.bricks.back().vbase = 16;
         total += 16;
     }
-    if (shift > 0 && last >= 0) {
-        int &vw = bp.rowd[2 * last + 1];
-        const int64_t o = (int64_t)(vw & (BRICK_ROW_NULL - 1)) + shift;
+    if (shift > 0 && s.last >= 0) {
+        const int64_t o = brick_row_off(bp.rowd.data(), s.last) + shift;
         KLE_ARG(o < BRICK_ROW_NULL, "shift beyond the descriptor's 23 bits");
-        vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)o;
+        brick_row_set_off(bp.rowd.data(), s.last, o);
     }
-    out[0] = rows;
-    out[1] = kept;
+    out[0] = s.rows;
+    out[1] = s.kept;
     out[2] = total;
     if (const char *bad = brick_validate(bp, Lx, Ly, Lz, total, (int64_t)bp.lds))
         return fail(KLE_ERR_SUP, "brick plan: %s", bad);
@@ -1025,35 +1054,10 @@ extern "C" int kle_brick_plan_box_runs(int Lx, int Ly, int Lz, int p, int dirich
     const int64_t n = (int64_t)Lx * Ly * Lz;
     std::vector<int> cnt, srow;
     (void)box_pattern(Lx, Ly, Lz, p, dirichlet, cnt, srow);
-    BrickPlan bp;
-    bp.singles = g_tune.spmv_brick_singles;
-    bp.pair = g_tune.spmv_brick_pair;
+    BrickPlan bp = brick_plan_inputs();
     const std::string why = brick_plan(Lx, Ly, Lz, 0, ncu, 0, 1, split, cnt, srow, p, bp);
     if (!why.empty()) return fail(KLE_ERR_SUP, "%s", why.c_str());
-    std::vector<std::pair<int, int64_t>> first;  // (packed box, offset of the row that keeps its values)
-    int64_t cur = 0;
-    for (BrickDesc &D : bp.bricks) {
-        for (int r = 0; r < D.nr; ++r) {
-            const int64_t rr = (int64_t)D.rstart + r;
-            if (brick_row_null(bp.rowd.data(), rr)) continue;
-            const int dw = bp.rowd[2 * rr] & 0xFFFFFF;
-            const int k0 = (dw & 15) + ((dw >> 12) & 15) * (((dw >> 4) & 15) + ((dw >> 16) & 15) * ((dw >> 8) & 15));
-            const int64_t mu = ((dw >> 12) & 15) * ((dw >> 16) & 15) * ((dw >> 20) & 15) - k0;
-            int64_t off = -1;
-            for (const auto &f : first)
-                if (f.first == dw) off = f.second;
-            if (off < 0) {
-                off = cur;
-                first.push_back({dw, off});
-                cur += (9 * mu + 15) & ~int64_t(15);
-            }
-            int &vw = bp.rowd[2 * rr + 1];
-            vw = (vw & ~(BRICK_ROW_NULL - 1)) | (int)(off >> 4);
-        }
-        D.vbase = 0;
-    }
-    bp.dedup = true;
-    const int64_t total = (cur + 9 * (int64_t)bp.srows.size() + 15) & ~int64_t(15);
+    const int64_t total = brick_share_by_box(bp).total;
     brick_runs_build(bp, G);
     int big = 0;
     for (int rv : bp.runs) big = std::max(big, brick_run_count(rv));

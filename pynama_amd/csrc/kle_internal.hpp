@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/kle.h"
@@ -390,6 +391,18 @@ int sval_alloc(kle_mat *A, size_t bytes);
 int big_alloc(void **p, size_t bytes);
 // host -> device, landed on return (hipMemcpy + the null stream's sync)
 int h2d(void *dst, const void *src, size_t bytes);
+// a temporary device allocation: freed when its scope ends, unless released
+template <class T>
+struct DevTmp {
+    T *p = nullptr;
+    DevTmp() = default;
+    explicit DevTmp(T *q) : p(q) {}
+    DevTmp(const DevTmp &) = delete;
+    DevTmp &operator=(const DevTmp &) = delete;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+    bool alloc(size_t count) { return hipMalloc(&p, sizeof(T) * count) == hipSuccess; }  // (count elements)
+    T *release() { return std::exchange(p, nullptr); }
+};
 // declare `bytes` of dynamic LDS for kernel `kern` on c's device (once per size)
 void dyn_lds(const kle_ctx *c, const void *kern, size_t bytes);
 // (xs: the owned x, for the box bricks' one-block rows -- d_ssingle)

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(64 * WV, 4) __attribute__((amdgpu_num_sgpr(SYM_XL_S
     // row cost as many instructions as the row's items
     auto slot_row = [&](int s, SymRow &R) {
         const int sx = slot_x(s), sy = slot_y(s), sz = s / NQ;  // the row in the tile
-        const int d = __builtin_amdgcn_readlane(pd, s);
+        const int d = __builtin_amdgcn_readlane(pd, s);  // (decoded as kle_brick.hpp brick_row_box defines it)
         const int dbx = d & 15, dby = (d >> 4) & 15, dbz = (d >> 8) & 15;
         R.bnx = (d >> 12) & 15;
         const int bny = (d >> 16) & 15, bnz = (d >> 20) & 15;
@@ -2017,15 +2017,6 @@ static int sym_probe(kle_mat *A, double vmax_all, bool &bad)
 // rank decides the same way (any_rank), so no rank runs the symmetric SpMV
 // and its reverse halo while a neighbour runs the full storage.
 static int sym_build_impl(kle_mat *A, bool full_first);
-// a device scratch buffer freed when its scope ends
-struct DevFree {
-    void *&p;
-    ~DevFree()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // Every error return of the builders, wherever it happens (a refused check,
 // a device error between the allocations and the last check), leaves A
 // without symmetric storage: no SpMV can run over a half-built copy.
@@ -2168,21 +2159,21 @@ static int sym_build_impl(kle_mat *A, bool full_first)
         // is stored as +0.0 (the check decides, on every rank alike)
         std::vector<unsigned char> rbits;
         if (g_tune.spmv_brick_compact && !full_first) {
-            unsigned long long *dc = nullptr, hc = 1;
-            unsigned char *db = nullptr;
-            DevFree fdc{(void *&)dc}, fdb{(void *&)db};  // (freed on every way out)
-            const bool mem = hipMalloc(&dc, sizeof(hc)) == hipSuccess && hipMalloc(&db, std::max<int64_t>(n, 1)) == hipSuccess;
+            unsigned long long hc = 1;
+            DevTmp<unsigned long long> dc;
+            DevTmp<unsigned char> db;
+            const bool mem = dc.alloc(1) && db.alloc(std::max<int64_t>(n, 1));
             (void)hipGetLastError();
             if (mem && dbmax <= 7 && n > 0) {
-                KLE_HIP(hipMemsetAsync(dc, 0, sizeof(hc), c->stream));
+                KLE_HIP(hipMemsetAsync(dc.p, 0, sizeof(hc), c->stream));
                 hipLaunchKernelGGL(k_brick_zero_check, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, n, (int)Lx,
                                    (int)Ly, (int)Lz, (int)zo, (int)(A->lo_rank < 0), (int)(A->hi_rank < 0), A->d_rowptr,
-                                   A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dc, db);
+                                   A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dc.p, db.p);
                 KLE_HIP(hipGetLastError());
                 KLE_HIP(hipStreamSynchronize(c->stream));
-                KLE_HIP(hipMemcpy(&hc, dc, sizeof(hc), hipMemcpyDeviceToHost));
+                KLE_HIP(hipMemcpy(&hc, dc.p, sizeof(hc), hipMemcpyDeviceToHost));
                 rbits.resize(n);
-                KLE_HIP(hipMemcpy(rbits.data(), db, n, hipMemcpyDeviceToHost));
+                KLE_HIP(hipMemcpy(rbits.data(), db.p, n, hipMemcpyDeviceToHost));
             }
             bool no = false;
             KLE_TRY(any_rank(c, hc != 0 || rbits.empty(), no));
@@ -2267,16 +2258,15 @@ static int sym_build_impl(kle_mat *A, bool full_first)
         if (compact) {
             std::vector<int> pd;
             brick_pack_desc(bplan, srow, pd);
-            int *dpd = nullptr;
-            DevFree fpd{(void *&)dpd};
-            if (hipMalloc(&dpd, sizeof(int) * std::max<int64_t>(n, 1)) != hipSuccess) {
+            DevTmp<int> dpd;
+            if (!dpd.alloc(std::max<int64_t>(n, 1))) {
                 (void)hipGetLastError();
                 nomem = 1;
             } else {
-                KLE_TRY(h2d(dpd, pd.data(), sizeof(int) * n));
+                KLE_TRY(h2d(dpd.p, pd.data(), sizeof(int) * n));
                 KLE_HIP(hipMemsetAsync(A->d_sval, 0, sizeof(double) * std::max<int64_t>(tot, 1), c->stream));
                 hipLaunchKernelGGL(k_brick_pack, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, n, (int)Lx,
-                                   (int)Ly, (int)zo, A->d_rowptr, A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dpd,
+                                   (int)Ly, (int)zo, A->d_rowptr, A->d_rowcnt, A->d_rowbox, A->d_vptr, A->d_val, dpd.p,
                                    A->d_svptr, A->d_sval);
                 KLE_HIP(hipGetLastError());
                 KLE_HIP(hipStreamSynchronize(c->stream));
