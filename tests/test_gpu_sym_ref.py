@@ -1,6 +1,6 @@
 """The symmetric-storage SpMV kernels and the CG that runs on them, row by row
 against longdouble references (tests/sym_ref.py, tests/krylov_ref.py).  One
-rank, 3-D.
+rank, 3-D; tests/test_gpu_sym_ranks_ref.py holds the same on several ranks.
 
 a. K x in every storage -- full, box bricks (planned, one brick, a forced
    split, one-block rows as brick items, unpaired rows, the gather with 1, 2
