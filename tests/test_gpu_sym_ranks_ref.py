@@ -152,9 +152,13 @@ def rank_setup(rank, size, port, cfg):
     return dist
 
 
-def build_system(pa, cfg, msh, operators):
+def build_system(pa, cfg, msh, operators, walls=None):
+    """Domain and MatFS of a configuration; with walls ({name: wall velocity},
+    in configuration order) the no-slip Domain and MatNS."""
     dim = 3 if cfg.get("gmsh") else len(cfg["nelem"])
     bc = {"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}}
+    if walls:
+        bc = {"no-slip": walls}
     if cfg.get("gmsh"):
         dcfg = {"ngl": cfg["ngl"], "gmsh-file": msh, "partitioner": cfg["gmsh"]}
     else:
@@ -162,7 +166,7 @@ def build_system(pa, cfg, msh, operators):
     dom = pa.Domain()
     dom.configure({"domain": dcfg, "boundary-conditions": bc})
     dom.setUp()
-    mat = pa.MatFS()
+    mat = pa.MatNS() if walls else pa.MatFS()
     mat.setDomain(dom)
     mat.build(buildOperators=operators)
     return dom, mat
@@ -251,13 +255,14 @@ def _worker(rank, size, port, cfg, msh, q):
         dist.destroy_process_group()
 
 
-def gmsh_file(tmp_path_factory):
-    if "msh" not in _RUNS:
+def gmsh_file(tmp_path_factory, nelem=None):
+    key = "msh" if nelem is None else ("msh",) + tuple(nelem)
+    if key not in _RUNS:
         from pynama_amd.meshgen import perturbed_box, write_gmsh
         path = str(tmp_path_factory.mktemp("ranksref") / "part.msh")
-        write_gmsh(path, 3, *perturbed_box(3, GMSH, seed=5))
-        _RUNS["msh"] = path
-    return _RUNS["msh"]
+        write_gmsh(path, 3, *perturbed_box(3, GMSH if nelem is None else list(nelem), seed=5))
+        _RUNS[key] = path
+    return _RUNS[key]
 
 
 def spawn(worker, cfg, msh):
