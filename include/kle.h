@@ -503,9 +503,10 @@ int kle_assemble_operators(kle_ctx *ctx, kle_mesh *m, kle_mat **Curl, kle_mat **
  * unstructured meshes, no-slip meshes and a mesh whose nranks is not the
  * context's. */
 int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
-/* Sum-factorised element-wise K (which 0) or Krhs (which 1) of any one-rank
- * mesh, kind 0 (box) or kind 1 (unstructured), 2-D or 3-D, ngl 2..8, with its
- * Dirichlet set: no stored values and no element matrix.  The factored form of
+/* Sum-factorised element-wise K (which 0) or Krhs (which 1) of any mesh, kind
+ * 0 (box) or kind 1 (unstructured), 2-D or 3-D, ngl 2..8, with its Dirichlet
+ * set, on one rank or on the parts of a partition (below): no stored values
+ * and no element matrix.  The factored form of
  * the element matrix,
  *     K_e(la, mb) = d_ab G_lm + a_d D_ab(l,m) + a_w (d_ab tr D(l,m) - D_ba(l,m)),
  *     G_lm = sum_full c_q grad N_l . grad N_m,  D_ab(l,m) = sum_red c_q d_a N_l d_b N_m,
@@ -540,15 +541,39 @@ int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **o
  * kle_ksp_set_operators with cg (classic and single reduction: the generic
  * paths), pipecg or gmres and PC none or jacobi.  Calls that need stored
  * values, and kle_mat_copy_dirichlet_rows, return KLE_ERR_SUP.
- * KLE_ERR_SUP also for which 2 (Rw: kle_mat_create_rw_sumfac), no-slip meshes, a mesh whose nranks is
- * not the context's and any mesh with nranks > 1; KLE_ERR_ARG for any other
+ * KLE_ERR_SUP also for which 2 (Rw: kle_mat_create_rw_sumfac), no-slip meshes
+ * and a mesh whose nranks is not the context's; KLE_ERR_ARG for any other
  * which.  Every table index is checked on the host before upload
- * (connectivity inside the mesh, incidence consistent with it and ascending,
- * E ngl^dim and dim N below 2^31): a bad table is an error code, never a
- * launch. */
+ * (connectivity inside the ext range, incidence consistent with it and
+ * ascending, the element lists disjoint, covering and true to their kind,
+ * E ngl^dim and dim times the ext nodes below 2^31): a bad table is an error
+ * code, never a launch.
+ * Several ranks (m->nranks == ctx->nranks > 1; box slabs, Gmsh slab and
+ * inertial partitions): a rank's local elements are every cell touching an
+ * owned node, ascending global cell id.  The connectivity holds ext-local node
+ * ids over all of them, masked by the Dirichlet flags of the ext range (a
+ * ghost Dirichlet column is dropped like an owned one).  x is a ghosted mesh
+ * vector (kle_vec_create_mesh; a graph partition's carries the mesh's halo
+ * plan), y covers the owned rows; sizes, ownership ranges and kle_mat_get_info
+ * are as for kle_mat_create_kle_element on ranks.  The incidence list, the
+ * gather and the diagonal cover the owned nodes, whose incident elements are
+ * all local: no communication.  The elements that read owned nodes alone are
+ * not contiguous in ascending-cell order, so the element kernels take an
+ * element list: the inner list (every entry, masked or not, an owned node)
+ * and the outer list (at least one ghost).  A product is one forward halo of
+ * x; with halo overlap on (kle_mat_set_halo_overlap, the default) the inner
+ * list runs on the compute stream beside the halo on the comm stream, the
+ * outer list after it, then the gather; with overlap off the halo first, then
+ * both lists; kle_mat_time_local_spmv runs both lists without the halo.  An
+ * empty list launches nothing.  The element results, the geometry tables and
+ * the connectivity stay indexed by the element's own id, so the owned rows
+ * are the one-rank product's bit for bit.  kle_mat_spmv_bytes counts the
+ * local elements, the ext range of x, the owned rows and the lists. */
 int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Sum-factorised element-wise Rw [dim N x dim_w N] (dim_w = 1 in 2-D, 3 in
- * 3-D) of any one-rank mesh, box or unstructured: the Rw of kle_assemble_kle
+ * 3-D) of any mesh, box or unstructured, one rank or several (as
+ * kle_mat_create_kle_sumfac: element lists, one forward halo of the ghosted w,
+ * owned rows bit-identical to the one-rank product): the Rw of kle_assemble_kle
  * with no assembled values and no element matrix,
  *     (Rw_e w)_l^a =  sum_{q in full} c_q N_l(q) (curl w)_a(q)
  *                   + a_w sum_{q in red} c_q sum_b d_b N_l(q) eps_{acb} w_c(q)
@@ -571,8 +596,8 @@ int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **ou
  * kle_mat_spmv_kernel ("k_sumfac_rw<D>+k_sumfac_gather_rw<D>") and
  * kle_mat_time_local_spmv.  KLE_ERR_SUP: kle_mat_get_diagonal,
  * kle_mat_copy_dirichlet_rows, every call that needs stored values, no-slip
- * meshes, a mesh whose nranks is not the context's and any mesh with
- * nranks > 1.  kle_ksp_set_operators refuses the non-square 2-D Rw before any
+ * meshes and a mesh whose nranks is not the context's.
+ * kle_ksp_set_operators refuses the non-square 2-D Rw before any
  * launch.  Every table index is checked on the host before upload. */
 int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out);
 /* Element-wise no-slip operator of a uniform box mesh: the matrices of
@@ -650,8 +675,8 @@ int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **ou
  * KLE_ERR_ARG for a bad which. */
 int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* The same collocation operators (which 0 Curl, 1 SrT, 2 DivSrT) with every
- * element's own geometry, on any one-rank mesh, box or unstructured, 2-D or
- * 3-D, ngl 2..8, free-slip or no-slip:
+ * element's own geometry, on any mesh, box or unstructured, 2-D or 3-D, ngl
+ * 2..8, free-slip or no-slip, one rank or several:
  *     y = Winv sum_e S_e^T M_e S_e^c x.
  * k_colloc_elem reads c_l and inv J of its own element from the nodal table
  * [E][nn][1 + dim^2] that the assembly's geometry kernel fills at the operator
@@ -665,8 +690,12 @@ int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int which, kle_ma
  * kle_mat_create_rw_sumfac.
  * Call surface and refusals as kle_mat_create_operator_element
  * (kle_mat_spmv_kernel: "k_colloc_elem<D,Op,geo>+k_colloc_gather_csr<RW>").
- * KLE_ERR_SUP for nranks > 1 and a mesh whose nranks is not the context's,
- * KLE_ERR_ARG for a bad which; connectivity and incidence are checked on the
+ * Several ranks: the tables, the two element lists and the halo pattern of
+ * kle_mat_create_kle_sumfac; winv is formed over the owned nodes, whose
+ * incident elements are all local; owned rows bit-identical to the one-rank
+ * product.
+ * KLE_ERR_SUP for a mesh whose nranks is not the context's, KLE_ERR_ARG for a
+ * bad which; connectivity, incidence and element lists are checked on the
  * host before upload. */
 int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Dense collocation element matrices of local element e as the assembly forms
@@ -833,9 +862,14 @@ int kle_mat_spmv_kernel(const kle_mat *A, char *buf, int buflen);
  * and the gather of every row they touch, with no halo exchange either way
  * (the ghost x as they are).  A part's own kernel time, free of its
  * neighbours -- ranks that share a GPU take turns.  Box-brick symmetric
- * storage (y's ghost-row sums are not sent) or an element-wise operator (its
+ * storage (y's ghost-row sums are not sent), an element-wise operator (its
  * element launches over this rank's local elements and the owned-row gather,
- * at any rank count); KLE_ERR_ARG otherwise. */
+ * at any rank count; a sum-factorised operator on ranks: both element lists),
+ * or, on several ranks, a rank's part of any other node-block matrix (every
+ * owned row; graph symmetric storage: its groups or bricks and the gather,
+ * the ghost rows' sums not sent; the box symmetric tiles are refused);
+ * KLE_ERR_ARG otherwise, as for a one-rank matrix without bricks, whose
+ * product is its local product. */
 int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, double *ms);
 
 /* -------------------------------------------------------------------- ksp */

@@ -1,6 +1,6 @@
 // kle_colloc.hip -- element-wise Curl, SrT and DivSrT (kle_mat kind 2 with
 // colloc set): no assembled values.  Of a uniform box mesh with one element's
-// geometry (kle_mat_create_operator_element), of any one-rank mesh with every
+// geometry (kle_mat_create_operator_element), of any mesh with every
 // element's own (kle_mat_create_operator_sumfac, at the end of this header).
 //
 // The operators (kle_assemble.hip "operators") are collocation operators on
@@ -41,7 +41,8 @@
 // global element 0 on every rank: the owned rows are the one-rank product's
 // bit for bit.
 //
-// Per-element geometry (any one-rank mesh, box or unstructured):
+// Per-element geometry (any mesh, box or unstructured; several ranks: the
+// element lists of kle_sumfac.hip):
 //
 //     y = Winv  sum over elements e of  S_e^T  M_e  S_e^c x,
 //
@@ -84,6 +85,7 @@ struct CollocOp {
     std::shared_ptr<GeoSet> geo;
     int32_t *d_incp = nullptr;  // [N + 1]
     int64_t ninc = 0;
+    int32_t *d_elist = nullptr;  // several ranks: [E] the inner, then the outer elements (kle_sumfac.hip)
 };
 
 // OP 0 Curl [dim_w x dim], 1 SrT [dim_s x dim], 2 DivSrT [dim x dim_s]
@@ -123,12 +125,16 @@ __host__ __device__ constexpr double colloc_coef(int a, int b, int d)
 }
 
 // PE: geo holds every element's table, [E][nn][G1], instead of the first element's
-template <int DIM, int OP, bool PE = false>
+// LIST: [eb, E) are positions of elist, which names the elements (several ranks
+// with PE: the inner or the outer list); conn, geo and ws stay indexed by the
+// element's own id, the LDS tile by its place in the batch
+template <int DIM, int OP, bool PE = false, bool LIST = false>
 __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t eb,
                                                      int64_t E,
                                                      const double *__restrict__ dh, const double *__restrict__ geo,
                                                      const int32_t *__restrict__ conn, const double *__restrict__ x,
-                                                     double *__restrict__ ws, const int *__restrict__ istate)
+                                                     double *__restrict__ ws, const int *__restrict__ istate,
+                                                     const int32_t *__restrict__ elist)
 {
     if (istate && istate[I_REASON] != 0) return;
     constexpr int CW = colloc_cw(DIM, OP), RW = colloc_rw(DIM, OP), G1 = 1 + DIM * DIM;
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, i
         const int el = t / nn, l = t - el * nn;
         const int i = l % ngl, r = l / ngl, j = DIM == 3 ? r % ngl : r, k = DIM == 3 ? r / ngl : 0;
         const int p = el * se + k * sz + j * sy + i;
-        const int64_t node = conn[t0 + t];
+        const int64_t node = conn[LIST ? (int64_t)elist[e0 + el] * nn + l : t0 + t];
 #pragma unroll
         for (int b = 0; b < CW; ++b) sx[b * SC + p] = x[node * CW + b];
     }
@@ -175,7 +181,8 @@ __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, i
 #pragma unroll
                 for (int d = 0; d < DIM; ++d) h[b][d] += dm[d] * sx[b * SC + o[d]];
         }
-        const double *g = PE ? geo + (t0 + t) * G1 : geo + l * G1;
+        const int64_t tg = LIST ? (int64_t)elist[e0 + el] * nn + l : t0 + t;  // the (element, node) pair's own index
+        const double *g = PE ? geo + tg * G1 : geo + l * G1;
         const double c = g[0];
         double Ji[DIM][DIM];
 #pragma unroll
@@ -192,7 +199,7 @@ __global__ __launch_bounds__(256) void k_colloc_elem(int ngl, int nn, int neb, i
                 for (int kk = 0; kk < DIM; ++kk) acc += Ji[d][kk] * h[b][kk];
                 H[b][d] = acc;
             }
-        double *out = ws + (t0 + t) * RW;
+        double *out = ws + tg * RW;
 #pragma unroll
         for (int a = 0; a < RW; ++a) {
             double s = 0.0;
@@ -276,11 +283,17 @@ template <int DIM, int OP>
 static void launch_colloc(const CollocOp *P, hipStream_t st, int64_t e0, int64_t e1, const double *x, double *y,
                           const int *istate)
 {
-    if (P->per_elem) {  // one rank: every element, then the CSR gather
+    if (P->per_elem) {  // every element (several ranks: positions [e0, e1) of the element lists), then the CSR gather
         if (e0 >= 0) {
             const unsigned ge = (unsigned)((e1 - e0 + P->neb - 1) / P->neb);
-            hipLaunchKernelGGL((k_colloc_elem<DIM, OP, true>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,
-                               P->sz, P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate);
+            if (P->d_elist)
+                hipLaunchKernelGGL((k_colloc_elem<DIM, OP, true, true>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn,
+                                   P->neb, P->sy, P->sz, P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate,
+                                   P->d_elist);
+            else
+                hipLaunchKernelGGL((k_colloc_elem<DIM, OP, true>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb,
+                                   P->sy, P->sz, P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate,
+                                   nullptr);
             return;
         }
         const unsigned gn = (unsigned)((P->N + 255) / 256);
@@ -291,7 +304,7 @@ static void launch_colloc(const CollocOp *P, hipStream_t st, int64_t e0, int64_t
     if (e0 >= 0) {
         const unsigned ge = (unsigned)((e1 - e0 + P->neb - 1) / P->neb);
         hipLaunchKernelGGL((k_colloc_elem<DIM, OP>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz,
-                           P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate);
+                           P->se, e0, e1, P->d_dh, P->d_geo, P->d_conn, x, P->d_ws, istate, nullptr);
         return;
     }
     const unsigned gn = (unsigned)((P->N + 255) / 256);
@@ -319,7 +332,8 @@ int colloc_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, boo
         return 0;
     };
     if (P->per_elem) {
-        KLE_TRY(launch(0, P->E));
+        if (!P->d_elist) KLE_TRY(launch(0, P->E));
+        else KLE_TRY(elem_ranges(A, x, local, [&](int64_t l0, int64_t l1, bool) -> int { return launch(l0, l1); }));
         return launch(-1, -1);
     }
     // (the ghost layer whole: a workgroup takes whole elements)
@@ -334,6 +348,7 @@ void colloc_drop(kle_mat *A)
     (void)hipFree(P->d_dh);
     if (!P->per_elem) (void)hipFree(P->d_geo);  // (else the mesh's set: it goes with its last holder)
     (void)hipFree(P->d_incp);
+    (void)hipFree(P->d_elist);
     (void)hipFree(P->d_winv);
     (void)hipFree(P->d_ws);
     (void)hipFree(P->d_conn);
@@ -351,9 +366,10 @@ double colloc_spmv_bytes(const kle_mat *A)
     const CollocOp *P = A->colloc;
     if (!P) return 0.0;
     if (P->per_elem)  // every element's geometry, the CSR list instead of the padded table
-        return 4.0 * P->E * P->nn + 8.0 * A->n_local + 8.0 * P->ngl * P->ngl +
+        // (several ranks: the local E, the ext range of x, the owned N and the element lists)
+        return 4.0 * P->E * P->nn + 8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * P->ngl * P->ngl +
                8.0 * P->E * P->nn * (1 + P->dim * P->dim) + 2.0 * 8.0 * P->E * P->nn * P->rw + 4.0 * (P->N + 1) +
-               4.0 * P->ninc + 8.0 * P->N + 8.0 * A->m_local;
+               4.0 * P->ninc + 8.0 * P->N + 8.0 * A->m_local + (P->d_elist ? 4.0 * P->E : 0.0);
     return 4.0 * P->E * P->nn + 8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 8.0 * P->ngl * P->ngl + 8.0 * P->nn * (1 + P->dim * P->dim) +
            2.0 * 8.0 * P->E * P->nn * P->rw + 4.0 * P->N * P->maxinc + 8.0 * P->N + 8.0 * A->m_local;
 }
@@ -536,43 +552,23 @@ extern "C" int kle_mat_create_operator_element(kle_ctx *ctx, kle_mesh *m, int wh
     return 0;
 }
 
-// The same operators with every element's own geometry: any one-rank mesh.
+// The same operators with every element's own geometry: any mesh, on one rank
+// or on the parts of a partition (tables, element lists and halo as kle_sumfac.hip;
+// winv over the owned nodes, whose incident elements are all local).
 extern "C" int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
 {
     KLE_ARG(ctx && m && out, "null arg");
     KLE_ARG(which >= 0 && which <= 2, "which must be 0 (Curl), 1 (SrT) or 2 (DivSrT)");
-    if (m->nranks != ctx->nranks)
-        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
-                    m->nranks, ctx->nranks);
-    if (m->nranks > 1) return fail(KLE_ERR_SUP, "sum-factorised operator: one rank only");
     const int dim = m->dim, ngl = m->ngl, nn = m->nn(), G1 = 1 + dim * dim;
     KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "sum-factorised operator: dim 2 or 3, ngl 2..8");
     const int rw = colloc_rw(dim, which), cw = colloc_cw(dim, which);
-    ElemLayout L;
-    L.N = L.next = m->node_end - m->node_begin;
-    L.E = L.eint1 = m->n_local_elems();
-    const int64_t E = L.E, N = L.N;
-    KLE_ARG(E >= 1 && N >= 1 && m->node_begin == 0 && m->ext_begin == 0 && m->ext_end == N && N == m->N,
-            "unexpected one-rank layout");
-    if (E * nn >= INT32_MAX || N * std::max(rw, cw) >= INT32_MAX)
-        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
 
-    // connectivity and CSR incidence list (host), validated before upload
-    std::vector<int64_t> conn64((size_t)E * nn);
-    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
-    std::vector<int32_t> conn((size_t)E * nn), incp((size_t)N + 1, 0), inc((size_t)E * nn, -1);
-    for (int64_t k = 0; k < E * nn; ++k) {
-        if (conn64[k] < 0 || conn64[k] >= N)
-            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld outside the mesh", (long long)k);
-        conn[k] = (int32_t)conn64[k];
-        ++incp[conn[k] + 1];
-    }
-    for (int64_t i = 0; i < N; ++i) incp[i + 1] += incp[i];
-    {
-        std::vector<int32_t> fill(incp.begin(), incp.end() - 1);
-        for (int64_t k = 0; k < E * nn; ++k) inc[fill[conn[k]]++] = (int32_t)k;  // k = e * nn + l, ascending e
-    }
-    KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, std::max(rw, cw)));
+    // connectivity in ext-local ids, the owned nodes' CSR incidence list and (several
+    // ranks) the element lists (host), validated before upload
+    ElemLayout L;
+    std::vector<int32_t> conn, incp, inc, elist;
+    KLE_TRY(sumfac_tables(ctx, m, std::max(rw, cw), &L, conn, incp, inc, elist));
+    const int64_t E = L.E, N = L.N;
     for (int64_t i = 0; i < N; ++i)
         if (incp[i + 1] == incp[i])
             return fail(KLE_ERR_STATE, "sum-factorised operator: node %lld lies in no element", (long long)i);
@@ -608,7 +604,10 @@ extern "C" int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int whi
     P->E = E;
     P->N = N;
     P->per_elem = true;
-    P->ninc = E * nn;
+    P->ninc = (int64_t)inc.size();
+    // (a graph partition: the column space's halo goes through the mesh's plan)
+    A->plan = m->plan;
+    A->ext_gid = m->ext_gid;
     auto up = [&](auto **dp, const void *src, size_t bytes) {
         if (hipMalloc(dp, bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -624,6 +623,7 @@ extern "C" int kle_mat_create_operator_sumfac(kle_ctx *ctx, kle_mesh *m, int whi
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
+    if (!rc && !elist.empty()) rc = up(&P->d_elist, elist.data(), sizeof(int32_t) * elist.size());
     if (!rc) rc = up(&P->d_winv, nullptr, sizeof(double) * (size_t)N);
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * rw);
     if (!rc) {

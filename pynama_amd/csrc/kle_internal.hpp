@@ -210,7 +210,7 @@ struct kle_vec {
 namespace kle {
 struct ElemOp;    // kle_elem.hip: the element-wise operator of a uniform box mesh
 struct CollocOp;  // kle_colloc.hip: an element-wise collocation operator (Curl, SrT, DivSrT)
-struct SumfacOp;  // kle_sumfac.hip: the sum-factorised K / Krhs of any one-rank mesh
+struct SumfacOp;  // kle_sumfac.hip: the sum-factorised K / Krhs / Rw of any mesh
 }
 
 struct kle_mat {
@@ -221,6 +221,7 @@ struct kle_mat {
     kle::SumfacOp *sumfac = nullptr;  // kind 2, instead of elem: sum-factorised K / Krhs (kle_sumfac.hip)
     // kind 2: el_n local elements -- [0, el_ghost) the ghost layer below, [el_ghost, el_int1) those reading
     // owned nodes alone (run beside the halo), [el_int1, el_n) the top layer reading the upper ghost plane
+    // (a sum-factorised operator on ranks: el_ghost 0, el_int1 the length of its inner element list)
     int64_t el_n = 0, el_ghost = 0, el_int1 = 0;
     int halo_overlap = 1;          // N>1: interior rows run while the halo is in flight
     int64_t int_lo = 0, int_hi = 0;  // rows [int_lo, int_hi) read no ghost entries
@@ -373,8 +374,8 @@ int nb_build_dict(kle_mat *A);  // kle_mat.hip
 int sym_build(kle_mat *A);
 void sym_drop(kle_mat *A);
 void sym_forget(kle_mat *A);  // null the symmetric-storage pointers of a struct copy (no free)
-int sym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate,
-             double *dpart = nullptr);  // N > 1: both halos included; dpart: (y, x) partials (one rank)
+int sym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart = nullptr,
+             bool local = false);  // N > 1: both halos included; dpart: (y, x) partials (one rank); local: graph storage without them (timing)
 int sym_dot_parts(const kle_mat *A);  // partials sym_spmv writes with dpart (0: it cannot)
 // brick symmetric SpMV (kle_brick.hip): plan (values in brick order: svptr
 // out; plan null + why when no brick decomposition applies), finish after the
@@ -495,13 +496,17 @@ struct GeoSet {
 // the mesh's set with F and R (kle) and / or O (ops) filled  (kle_assemble.hip)
 int mesh_geometry(kle_ctx *ctx, kle_mesh *m, bool kle, bool ops, std::shared_ptr<GeoSet> *out);
 // sum-factorised K, Krhs and Rw (kle_sumfac.hip; kle_mat kind 2 with sumfac set)
-int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate);
+int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local = false);
 int sumfac_diagonal(const kle_mat *A, kle_vec *d);
 void sumfac_drop(kle_mat *A);
 double sumfac_spmv_bytes(const kle_mat *A);
 std::string sumfac_kernel_name(const kle_mat *A);
+// (next < 0: one rank, the ext range is the N owned nodes; elist: the two element lists of a rank's part)
 int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &incp, const std::vector<int32_t> &inc,
-                    int64_t E, int64_t N, int nn, int dim);
+                    int64_t E, int64_t N, int nn, int dim, int64_t next = -1, int64_t own0 = 0,
+                    const std::vector<int32_t> *elist = nullptr, int64_t n_inner = 0);
+int sumfac_tables(const kle_ctx *ctx, const kle_mesh *m, int bw, ElemLayout *L, std::vector<int32_t> &conn,
+                  std::vector<int32_t> &incp, std::vector<int32_t> &inc, std::vector<int32_t> &elist);
 // kind 2 holds no assembled values: the calls that need them end here
 #define KLE_NO_ELEM(A, what)                                                                              \
     do {                                                                                                  \

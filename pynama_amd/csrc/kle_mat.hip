@@ -639,7 +639,7 @@ bool spmv_uses_comm_stream(const kle_mat *A, const kle_vec *x)
     // (an element-wise operator: where it has elements that read no ghost node)
     if (A->kind == 2)
         return A->ctx->nranks > 1 && A->halo_overlap && A->el_ghost < A->el_int1 &&
-               (x->lo_rank >= 0 || x->hi_rank >= 0);
+               (x->lo_rank >= 0 || x->hi_rank >= 0 || (x->plan && !x->plan->peers.empty()));
     return A->kind == 0 && A->ctx->nranks > 1 && A->halo_overlap &&
            (A->int_lo < A->int_hi || (A->d_sval && g_tune.spmv_sym)) &&
            (x->lo_rank >= 0 || x->hi_rank >= 0 || (x->plan && !x->plan->peers.empty()));
@@ -1718,13 +1718,23 @@ int kle_mat_time_local_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, int reps, 
 {
     KLE_ARG(A && x && y && ms && reps >= 1, "bad arg");
     KLE_TRY(check_mult_layout(A, x, y));
-    KLE_ARG(A->kind == 2 || spmv_can_split(A),
-            "local product timing: box-brick symmetric storage or an element-wise operator only");
     kle_ctx *c = A->ctx;
+    // a rank's part of an assembled node-block matrix (N > 1; on one rank the
+    // product itself is the local product): every owned row without the halo,
+    // graph symmetric storage without its two halos
+    const bool sym = A->kind == 0 && A->d_sval && g_tune.spmv_sym;
+    const bool nb_part = A->kind == 0 && c->nranks > 1 && !spmv_can_split(A) && (!sym || A->sym_graph);
+    KLE_ARG(A->kind == 2 || spmv_can_split(A) || nb_part,
+            "local product timing: box-brick symmetric storage, an element-wise operator or a rank's part of a "
+            "node-block matrix only");
     // an element-wise operator: this rank's element launches and its gather
     auto local = [&]() {
+        if (nb_part)
+            return sym ? sym_spmv(A, x, y, nullptr, nullptr, true)
+                       : launch_nb_shape(A, RowMap{0, A->nrows, 0, 0}, A->spmv_struct ? A->d_rowbox : nullptr, x, y,
+                                         nullptr, c->stream);
         return A->kind != 2 ? brick_spmv_local(A, x, y)
-               : A->sumfac  ? sumfac_spmv(A, x, y, nullptr)  // (one rank: no halo to leave out)
+               : A->sumfac  ? sumfac_spmv(A, x, y, nullptr, true)
                : A->colloc  ? colloc_spmv(A, x, y, nullptr, true)
                             : elem_spmv(A, x, y, nullptr, true);
     };

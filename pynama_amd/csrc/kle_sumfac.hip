@@ -1,6 +1,6 @@
-// kle_sumfac.hip -- sum-factorised element-wise K, Krhs and Rw on any one-rank
-// mesh, box or unstructured (kle_mat kind 2 with sumfac set): no assembled
-// values and no element matrix.
+// kle_sumfac.hip -- sum-factorised element-wise K, Krhs and Rw on any mesh, box
+// or unstructured, on one rank or on the parts of a partition (kle_mat kind 2
+// with sumfac set): no assembled values and no element matrix.
 //
 // On distorted hexes the element matrices differ, so the one K_e0 of
 // kle_elem.hip is gone; the factored form of the assembly (kle_assemble.hip
@@ -64,8 +64,21 @@
 // assembled matrix was formed from; K, Krhs and Rw of one mesh share them
 // (mesh_geometry).  No atomics, fixed order: the same input
 // gives the same bits.  Both product kernels do nothing once the Krylov reason
-// word is set.  One rank only: the index-list halos of a graph partition are
-// not handled.
+// word is set.
+//
+// Several ranks (box slabs; Gmsh slab and inertial partitions): a rank's local
+// elements are every cell touching an owned node, ascending global cell id;
+// conn holds ext-local node ids over all of them, masked by the Dirichlet flags
+// of the ext range (a ghost Dirichlet column is dropped like an owned one); x
+// is read through the vector's ghosted allocation after one forward halo (the
+// vector's plan on a graph partition); the incidence list, the gather and the
+// diagonal cover the owned nodes, whose incident elements are all local.  The
+// elements reading owned nodes alone are not contiguous in that order, so the
+// element kernels take an element list (LIST): inner, run on the compute
+// stream beside the halo on the comm stream, and outer, run after it
+// (elem_ranges over list positions: el_ghost 0, el_int1 the inner list's length).  ws, the geometry tables and conn stay indexed by the element's
+// own id, so the gather sums a node's entries in the one-rank order: the owned
+// rows are the one-rank product's bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -96,14 +109,21 @@ struct SumfacOp {
     int32_t *d_incp = nullptr;  // [N + 1] node -> its entries of d_inc
     int32_t *d_inc = nullptr;   // [E nn] e * nn + l, ascending e per node
     uint8_t *d_dir = nullptr;   // [N] Dirichlet flag
+    // several ranks: the local elements as two lists, [0, n_inner) those reading
+    // owned nodes alone, [n_inner, E) those reading a ghost; each ascending
+    int32_t *d_elist = nullptr;  // [E] (one rank: none, the kernels take every element in order)
 };
 
-template <int DIM>
+// LIST: the batch's elements are elist[e0 .. e0 + neb) of the E listed (several
+// ranks: the inner or the outer list); conn, geo and ws stay indexed by the
+// element's own id, the LDS tile by its place in the batch
+template <int DIM, bool LIST = false>
 __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
                                                      int negate, const double *__restrict__ tab,
                                                      const double *__restrict__ geoF, const double *__restrict__ geoR,
                                                      const int32_t *__restrict__ conn, const double *__restrict__ x,
-                                                     double *__restrict__ ws, const int *__restrict__ istate)
+                                                     double *__restrict__ ws, const int *__restrict__ istate,
+                                                     const int32_t *__restrict__ elist)
 {
     if (istate && istate[I_REASON] != 0) return;
     constexpr int NIT = DIM == 3 ? 2 : 1;  // sites per thread: 512 at ngl 8 in 3-D
@@ -126,11 +146,13 @@ __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, i
     }
     bool ok[NIT];
     int base[NIT], si[NIT], sj[NIT], sk[NIT], sel[NIT];
+    int64_t eid[NIT];  // the element's own id
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int t = tid + it * 256;
         ok[it] = t < nt;
         const int el = t / nn, l = t - el * nn;
+        eid[it] = LIST && ok[it] ? elist[e0 + el] : 0;
         const int r = l / ngl;
         si[it] = l % ngl;
         sj[it] = DIM == 3 ? r % ngl : r;
@@ -138,7 +160,7 @@ __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, i
         sel[it] = el;
         base[it] = el * se + sk[it] * sz + sj[it] * sy + si[it];
         if (ok[it]) {
-            const int node = conn[t0 + t];
+            const int node = conn[LIST ? eid[it] * nn + l : t0 + t];
 #pragma unroll
             for (int b = 0; b < DIM; ++b) {
                 double v = 0.0;
@@ -226,7 +248,7 @@ __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, i
         for (int it = 0; it < NIT; ++it) {
             if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
             const int q = (sk[it] * P + sj[it]) * P + si[it];
-            const double *gp = geo + ((e0 + sel[it]) * nq + q) * G1;
+            const double *gp = geo + ((LIST ? eid[it] : e0 + sel[it]) * nq + q) * G1;
             const double c = gp[0];
             double Ji[DIM][DIM];
 #pragma unroll
@@ -329,7 +351,7 @@ __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, i
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         if (!ok[it]) continue;
-        double *out = ws + (t0 + tid + it * 256) * DIM;
+        double *out = ws + (LIST ? eid[it] * nn + (tid + it * 256 - sel[it] * nn) : t0 + tid + it * 256) * DIM;
 #pragma unroll
         for (int a = 0; a < DIM; ++a) out[a] = negate ? -res[it][a] : res[it][a];
     }
@@ -359,12 +381,12 @@ __global__ __launch_bounds__(256) void k_sumfac_gather(int64_t N, const int32_t 
 
 // Rw_e w of a batch of whole elements: see the header.  The tiles, strides,
 // tables and site decoding are k_sumfac_elem's.
-template <int DIM>
+template <int DIM, bool LIST = false>
 __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
                                                    const double *__restrict__ tab, const double *__restrict__ geoF,
                                                    const double *__restrict__ geoR, const int32_t *__restrict__ conn,
                                                    const double *__restrict__ x, double *__restrict__ ws,
-                                                   const int *__restrict__ istate)
+                                                   const int *__restrict__ istate, const int32_t *__restrict__ elist)
 {
     if (istate && istate[I_REASON] != 0) return;
     constexpr int NIT = DIM == 3 ? 2 : 1;  // sites per thread: 512 at ngl 8 in 3-D
@@ -388,11 +410,13 @@ __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int
     }
     bool ok[NIT];
     int base[NIT], si[NIT], sj[NIT], sk[NIT], sel[NIT];
+    int64_t eid[NIT];  // the element's own id
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int t = tid + it * 256;
         ok[it] = t < nt;
         const int el = t / nn, l = t - el * nn;
+        eid[it] = LIST && ok[it] ? elist[e0 + el] : 0;
         const int r = l / ngl;
         si[it] = l % ngl;
         sj[it] = DIM == 3 ? r % ngl : r;
@@ -400,7 +424,7 @@ __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int
         sel[it] = el;
         base[it] = el * se + sk[it] * sz + sj[it] * sy + si[it];
         if (ok[it]) {
-            const int64_t node = conn[t0 + t];  // (Rw drops no column)
+            const int64_t node = conn[LIST ? eid[it] * nn + l : t0 + t];  // (Rw drops no column)
 #pragma unroll
             for (int b = 0; b < DW; ++b) sx[b * SC + base[it]] = x[node * DW + b];
         }
@@ -484,7 +508,7 @@ __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int
         for (int it = 0; it < NIT; ++it) {
             if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
             const int q = (sk[it] * P + sj[it]) * P + si[it];
-            const double *gp = geoF + ((e0 + sel[it]) * nq + q) * G1;
+            const double *gp = geoF + ((LIST ? eid[it] : e0 + sel[it]) * nq + q) * G1;
             const double c = gp[0];
             double Ji[DIM][DIM];
 #pragma unroll
@@ -635,7 +659,7 @@ __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int
         for (int it = 0; it < NIT; ++it) {
             if (!(ok[it] && si[it] < P && sj[it] < P && sk[it] < P)) continue;
             const int q = (sk[it] * P + sj[it]) * P + si[it];
-            const double *gp = geoR + ((e0 + sel[it]) * nq + q) * G1;
+            const double *gp = geoR + ((LIST ? eid[it] : e0 + sel[it]) * nq + q) * G1;
             const double c = gp[0];
             double Ji[DIM][DIM];
 #pragma unroll
@@ -721,7 +745,7 @@ __global__ __launch_bounds__(256) void k_sumfac_rw(int ngl, int nn, int neb, int
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         if (!ok[it]) continue;
-        double *out = ws + (t0 + tid + it * 256) * DIM;
+        double *out = ws + (LIST ? eid[it] * nn + (tid + it * 256 - sel[it] * nn) : t0 + tid + it * 256) * DIM;
 #pragma unroll
         for (int a = 0; a < DIM; ++a) out[a] = res[it][a];
     }
@@ -832,30 +856,60 @@ __global__ __launch_bounds__(256) void k_sumfac_diag_gather(int64_t N, int which
     d[i] = s;
 }
 
+// the element kernel over every element in order (list null: one rank), or
+// over the n elements list names
 template <int DIM>
-static void launch_sumfac(const SumfacOp *P, hipStream_t st, const double *x, double *y, const int *istate)
+static void launch_sumfac_elems(const SumfacOp *P, hipStream_t st, const int32_t *list, int64_t n, const double *x,
+                                const int *istate)
 {
-    const unsigned ge = (unsigned)((P->E + P->neb - 1) / P->neb), gn = (unsigned)((P->N * DIM + 255) / 256);
-    if (P->which == 2) {
-        hipLaunchKernelGGL(k_sumfac_rw<DIM>, dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se, P->E,
-                           P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate);
-        hipLaunchKernelGGL(k_sumfac_gather_rw<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir,
-                           P->d_ws, y, istate);
-        return;
-    }
-    hipLaunchKernelGGL(k_sumfac_elem<DIM>, dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy, P->sz, P->se, P->E,
-                       P->negate, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate);
-    hipLaunchKernelGGL(k_sumfac_gather<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir, P->d_ws,
-                       x, y, istate);
+    const unsigned ge = (unsigned)((n + P->neb - 1) / P->neb);
+#define KLE_SUMFAC_ELEMS(LIST)                                                                                        \
+    do {                                                                                                              \
+        if (P->which == 2)                                                                                            \
+            hipLaunchKernelGGL((k_sumfac_rw<DIM, LIST>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,    \
+                               P->sz, P->se, n, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate, list); \
+        else                                                                                                          \
+            hipLaunchKernelGGL((k_sumfac_elem<DIM, LIST>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,  \
+                               P->sz, P->se, n, P->negate, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws,     \
+                               istate, list);                                                                         \
+    } while (0)
+    if (list) KLE_SUMFAC_ELEMS(true);
+    else KLE_SUMFAC_ELEMS(false);
+#undef KLE_SUMFAC_ELEMS
 }
 
-int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate)
+// the owned rows' gather (x: the owned part; Rw never reads it)
+template <int DIM>
+static void launch_sumfac_gather(const SumfacOp *P, hipStream_t st, const double *x, double *y, const int *istate)
+{
+    const unsigned gn = (unsigned)((P->N * DIM + 255) / 256);
+    if (P->which == 2)
+        hipLaunchKernelGGL(k_sumfac_gather_rw<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir,
+                           P->d_ws, y, istate);
+    else
+        hipLaunchKernelGGL(k_sumfac_gather<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir,
+                           P->d_ws, x, y, istate);
+}
+
+int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local)
 {
     const SumfacOp *P = A->sumfac;
     if (!P) return fail(KLE_ERR_STATE, "sum-factorised operator without tables");
     KLE_TRY(elem_check_vecs(A, x, y, "sum-factorised operator"));
-    if (P->dim == 2) launch_sumfac<2>(P, A->ctx->stream, x->d, y->d, istate);
-    else launch_sumfac<3>(P, A->ctx->stream, x->d, y->d, istate);
+    hipStream_t st = A->ctx->stream;
+    // (x: the ghosted allocation, read in ext-local ids)
+    auto elems = [&](const int32_t *list, int64_t n) -> int {
+        if (P->dim == 2) launch_sumfac_elems<2>(P, st, list, n, x->base, istate);
+        else launch_sumfac_elems<3>(P, st, list, n, x->base, istate);
+        KLE_HIP(hipGetLastError());
+        return 0;
+    };
+    if (!P->d_elist) KLE_TRY(elems(nullptr, P->E));
+    else  // list positions [0, el_int1) inner, the rest outer: elem_ranges' interior and top layer, no ghost layer
+        KLE_TRY(elem_ranges(A, x, local,
+                            [&](int64_t l0, int64_t l1, bool) -> int { return elems(P->d_elist + l0, l1 - l0); }));
+    if (P->dim == 2) launch_sumfac_gather<2>(P, st, x->d, y->d, istate);
+    else launch_sumfac_gather<3>(P, st, x->d, y->d, istate);
     KLE_HIP(hipGetLastError());
     return 0;
 }
@@ -882,6 +936,7 @@ void sumfac_drop(kle_mat *A)
     (void)hipFree(P->d_incp);
     (void)hipFree(P->d_inc);
     (void)hipFree(P->d_dir);
+    (void)hipFree(P->d_elist);
     delete P;
     A->sumfac = nullptr;
 }
@@ -893,13 +948,16 @@ static int64_t sf_ipow(int b, int d) { return d == 2 ? (int64_t)b * b : (int64_t
 // once (8 n), the element results written (8 E nn dim).  k_sumfac_gather: the
 // incidence list (4 (N + 1) + 4 E nn), the Dirichlet flags (N), the element
 // results read, y written (8 m).  Rw: the same streams with its own n.
+// Several ranks: E the local elements, n the ext range of x, N the owned
+// nodes, and the two element lists (4 E).
 double sumfac_spmv_bytes(const kle_mat *A)
 {
     const SumfacOp *P = A->sumfac;
     if (!P) return 0.0;
     const double nq = (double)(sf_ipow(P->npF, P->dim) + sf_ipow(P->npR, P->dim));
-    return 4.0 * P->E * P->nn + 8.0 * P->E * nq * (1 + P->dim * P->dim) + 8.0 * 4 * P->ngl * P->ngl + 8.0 * A->n_local +
-           2.0 * 8.0 * P->E * P->nn * P->dim + 4.0 * (P->N + 1) + 4.0 * P->ninc + 1.0 * P->N + 8.0 * A->m_local;
+    return 4.0 * P->E * P->nn + 8.0 * P->E * nq * (1 + P->dim * P->dim) + 8.0 * 4 * P->ngl * P->ngl +
+           8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 2.0 * 8.0 * P->E * P->nn * P->dim + 4.0 * (P->N + 1) +
+           4.0 * P->ninc + 1.0 * P->N + 8.0 * A->m_local + (P->d_elist ? 4.0 * P->E : 0.0);
 }
 
 std::string sumfac_kernel_name(const kle_mat *A)
@@ -913,35 +971,131 @@ std::string sumfac_kernel_name(const kle_mat *A)
 
 // Every index the device tables hold, checked on the host before upload: a
 // bad table is an error code, never an out-of-range access.  conn [E][nn]
-// (unmasked) names nodes in [0, N); node i's incidence entries
-// inc[incp[i] .. incp[i + 1]) are positions of conn that name i, their
-// elements strictly ascending, and together they cover conn.
+// (unmasked) names ext-local nodes in [0, next), the owned ones [own0, own0 + N)
+// (one rank: next = N, own0 = 0).  Owned node i's incidence entries
+// inc[incp[i] .. incp[i + 1]) are positions of conn that name it, their
+// elements strictly ascending, and together they cover every position of conn
+// that names an owned node.  elist (several ranks, else null): [0, n_inner)
+// and [n_inner, E) each ascend, are disjoint and cover the elements; an inner
+// element names owned nodes only, an outer one at least one ghost.
 int sumfac_validate(const std::vector<int32_t> &conn, const std::vector<int32_t> &incp,
-                    const std::vector<int32_t> &inc, int64_t E, int64_t N, int nn, int dim)
+                    const std::vector<int32_t> &inc, int64_t E, int64_t N, int nn, int dim, int64_t next, int64_t own0,
+                    const std::vector<int32_t> *elist, int64_t n_inner)
 {
+    if (next < 0) next = N;
     if (E < 1 || N < 1 || nn < 1) return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: empty mesh");
-    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
+    if (own0 < 0 || own0 + N > next)
+        return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: the owned nodes lie outside the ext range");
+    if (E * nn >= INT32_MAX || next * dim >= INT32_MAX)
         return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
-    if ((int64_t)conn.size() != E * nn || (int64_t)incp.size() != N + 1 || (int64_t)inc.size() != E * nn)
+    if ((int64_t)conn.size() != E * nn || (int64_t)incp.size() != N + 1)
         return fail(KLE_ERR_SIZ, "sum-factorised operator: table sizes do not match the mesh");
-    for (int64_t k = 0; k < E * nn; ++k)
-        if (conn[k] < 0 || conn[k] >= N)
+    int64_t nowned = 0;
+    for (int64_t k = 0; k < E * nn; ++k) {
+        if (conn[k] < 0 || conn[k] >= next)
             return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld = %d outside [0, %lld)",
-                        (long long)k, conn[k], (long long)N);
-    if (incp[0] != 0 || incp[N] != E * nn)
+                        (long long)k, conn[k], (long long)next);
+        nowned += conn[k] >= own0 && conn[k] < own0 + N;
+    }
+    if ((int64_t)inc.size() != nowned)
+        return fail(KLE_ERR_SIZ, "sum-factorised operator: table sizes do not match the mesh");
+    if (incp[0] != 0 || incp[N] != nowned)
         return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: the incidence list does not cover the connectivity");
     for (int64_t i = 0; i < N; ++i) {
-        if (incp[i + 1] < incp[i] || incp[i + 1] > E * nn)
+        if (incp[i + 1] < incp[i] || incp[i + 1] > nowned)
             return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: incidence offsets of node %lld descend", (long long)i);
         int64_t prev = -1;
         for (int32_t j = incp[i]; j < incp[i + 1]; ++j) {
             const int32_t t = inc[j];
-            if (t < 0 || (int64_t)t >= E * nn || conn[t] != i || t / nn <= prev)
+            if (t < 0 || (int64_t)t >= E * nn || conn[t] != i + own0 || t / nn <= prev)
                 return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: incidence entry %d of node %lld is inconsistent",
                             j - incp[i], (long long)i);
             prev = t / nn;
         }
     }
+    if (!elist) return 0;
+    if ((int64_t)elist->size() != E || n_inner < 0 || n_inner > E)
+        return fail(KLE_ERR_SIZ, "sum-factorised operator: the element lists do not match the mesh");
+    std::vector<uint8_t> seen((size_t)E, 0);
+    for (int64_t k = 0; k < E; ++k) {
+        const int32_t e = (*elist)[k];
+        if (e < 0 || e >= E || seen[e] || (k > 0 && k != n_inner && e <= (*elist)[k - 1]))
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: element list entry %lld = %d is out of range, "
+                                            "repeated or out of order", (long long)k, e);
+        seen[e] = 1;
+        bool ghost = false;
+        for (int l = 0; l < nn; ++l) ghost |= conn[(int64_t)e * nn + l] < own0 || conn[(int64_t)e * nn + l] >= own0 + N;
+        if (ghost != (k >= n_inner))
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: %s element %d %s", k < n_inner ? "inner" : "outer",
+                        e, k < n_inner ? "names a ghost node" : "names no ghost node");
+    }
+    return 0;  // (E distinct entries in [0, E): the lists cover the elements)
+}
+
+// The host tables of a sum-factorised operator on ctx's part of m, validated:
+// the layout (L.eint1 the inner elements), conn [E][nn] in ext-local ids
+// (unmasked), the CSR incidence list of the owned nodes, ascending local
+// element (= ascending global cell id), and on several ranks the element
+// lists, inner then outer.  bw: the operator's widest block.
+int sumfac_tables(const kle_ctx *ctx, const kle_mesh *m, int bw, ElemLayout *Lout, std::vector<int32_t> &conn,
+                  std::vector<int32_t> &incp, std::vector<int32_t> &inc, std::vector<int32_t> &elist)
+{
+    if (m->nranks != ctx->nranks)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
+                    m->nranks, ctx->nranks);
+    KLE_ARG(m->rank == ctx->rank, "mesh partition does not match ctx");
+    const int nn = m->nn();
+    ElemLayout L;
+    L.N = m->node_end - m->node_begin;
+    L.next = m->ext_end - m->ext_begin;
+    L.own0 = m->node_begin - m->ext_begin;
+    L.E = L.eint1 = m->n_local_elems();
+    const int64_t E = L.E, N = L.N;
+    KLE_ARG(E >= 1 && N >= 1 && L.own0 >= 0 && L.own0 + N <= L.next &&
+                (m->nranks > 1 || (m->node_begin == 0 && L.own0 == 0 && L.next == N && N == m->N)),
+            "unexpected mesh layout");
+    if (E * nn >= INT32_MAX || L.next * bw >= INT32_MAX)
+        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
+    // (a graph partition's u_conn holds the pseudo ids ext_begin + ext position)
+    std::vector<int64_t> conn64((size_t)E * nn);
+    if (m->kind == 1) {
+        if ((int64_t)m->u_conn.size() != E * nn)
+            return fail(KLE_ERR_SIZ, "sum-factorised operator: the connectivity does not match the mesh");
+        conn64 = m->u_conn;
+    } else {
+        KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
+    }
+    conn.assign((size_t)E * nn, 0);
+    incp.assign((size_t)N + 1, 0);
+    for (int64_t k = 0; k < E * nn; ++k) {
+        const int64_t g = conn64[k] - m->ext_begin;
+        if (g < 0 || g >= L.next)
+            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld outside the mesh", (long long)k);
+        conn[k] = (int32_t)g;
+        if (g >= L.own0 && g < L.own0 + N) ++incp[g - L.own0 + 1];  // (a ghost node: read, never written)
+    }
+    for (int64_t i = 0; i < N; ++i) incp[i + 1] += incp[i];
+    inc.assign((size_t)incp[N], -1);
+    {
+        std::vector<int32_t> fill(incp.begin(), incp.end() - 1);
+        for (int64_t k = 0; k < E * nn; ++k) {
+            const int64_t o = conn[k] - L.own0;
+            if (o >= 0 && o < N) inc[fill[o]++] = (int32_t)k;  // k = e * nn + l, ascending e
+        }
+    }
+    elist.clear();
+    if (m->nranks > 1) {
+        std::vector<int32_t> outer;
+        for (int64_t e = 0; e < E; ++e) {
+            bool ghost = false;
+            for (int l = 0; l < nn; ++l) ghost |= conn[e * nn + l] < L.own0 || conn[e * nn + l] >= L.own0 + N;
+            (ghost ? outer : elist).push_back((int32_t)e);
+        }
+        L.eint1 = (int64_t)elist.size();
+        elist.insert(elist.end(), outer.begin(), outer.end());
+    }
+    KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, bw, L.next, L.own0, m->nranks > 1 ? &elist : nullptr, L.eint1));
+    *Lout = L;
     return 0;
 }
 
@@ -953,41 +1107,19 @@ using namespace kle;
 static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
 {
     if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "sum-factorised operator: no-slip meshes are not supported");
-    if (m->nranks != ctx->nranks)
-        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh is partitioned for %d ranks, the context has %d",
-                    m->nranks, ctx->nranks);
-    if (m->nranks > 1) return fail(KLE_ERR_SUP, "sum-factorised operator: one rank only");
-    const int dim = m->dim, ngl = m->ngl, nn = m->nn(), G1 = 1 + dim * dim;
+    const int dim = m->dim, ngl = m->ngl, nn = m->nn();
     KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "sum-factorised operator: dim 2 or 3, ngl 2..8");
-    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+    // tables (host) in ext-local ids, validated before upload
     ElemLayout L;
-    L.N = L.next = m->node_end - m->node_begin;
-    L.E = L.eint1 = m->n_local_elems();
+    std::vector<int32_t> conn, incp, inc, elist;
+    KLE_TRY(sumfac_tables(ctx, m, dim, &L, conn, incp, inc, elist));
+    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
     const int64_t E = L.E, N = L.N;
-    KLE_ARG(E >= 1 && N >= 1 && m->node_begin == 0 && m->ext_begin == 0 && m->ext_end == N && N == m->N,
-            "unexpected one-rank layout");
-    if ((int64_t)m->dir.size() != N) return fail(KLE_ERR_SIZ, "sum-factorised operator: Dirichlet flags do not match the mesh");
-    if (E * nn >= INT32_MAX || N * dim >= INT32_MAX)
-        return fail(KLE_ERR_SUP, "sum-factorised operator: the mesh exceeds the 32-bit tables");
-
-    // tables (host), validated before upload
-    std::vector<int64_t> conn64((size_t)E * nn);
-    KLE_TRY(kle_mesh_get_conn(m, conn64.data()));
-    std::vector<int32_t> conn((size_t)E * nn), incp((size_t)N + 1, 0), inc((size_t)E * nn, -1);
-    for (int64_t k = 0; k < E * nn; ++k) {
-        if (conn64[k] < 0 || conn64[k] >= N)
-            return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: connectivity entry %lld outside the mesh", (long long)k);
-        conn[k] = (int32_t)conn64[k];
-        ++incp[conn[k] + 1];
-    }
-    for (int64_t i = 0; i < N; ++i) incp[i + 1] += incp[i];
-    {
-        std::vector<int32_t> fill(incp.begin(), incp.end() - 1);
-        for (int64_t k = 0; k < E * nn; ++k) inc[fill[conn[k]]++] = (int32_t)k;  // k = e * nn + l, ascending e
-    }
-    KLE_TRY(sumfac_validate(conn, incp, inc, E, N, nn, dim));
+    if ((int64_t)m->dir.size() != L.next)
+        return fail(KLE_ERR_SIZ, "sum-factorised operator: Dirichlet flags do not match the mesh");
     // the mask rule folded into the connectivity the element kernel reads: K
-    // drops the Dirichlet entries of x, Krhs the free ones
+    // drops the Dirichlet entries of x (ghosts included: m->dir covers the ext
+    // range), Krhs the free ones
     // (Rw drops nothing)
     for (int64_t k = 0; k < E * nn && which != 2; ++k)
         if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
@@ -1030,7 +1162,10 @@ static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
     P->npR = npR;
     P->E = E;
     P->N = N;
-    P->ninc = E * nn;
+    P->ninc = (int64_t)inc.size();
+    // (a graph partition: the column space's halo goes through the mesh's plan)
+    A->plan = m->plan;
+    A->ext_gid = m->ext_gid;
     auto up = [&](auto **dp, const void *src, size_t bytes) {
         if (hipMalloc(dp, bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -1052,7 +1187,8 @@ static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
-    if (!rc) rc = up(&P->d_dir, m->dir.data(), (size_t)N);
+    if (!rc) rc = up(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
+    if (!rc && !elist.empty()) rc = up(&P->d_elist, elist.data(), sizeof(int32_t) * elist.size());
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * dim);
     if (!rc && which != 2) rc = up(&P->d_diag, nullptr, sizeof(double) * (size_t)N * dim);
     if (!rc && which != 2) {

@@ -1755,7 +1755,9 @@ int gsym_gather(kle_mat *A, double *y, int64_t r0, int64_t r1, const int *istate
     return 0;
 }
 
-static int gsym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart)
+// (local: this rank's launches alone -- no forward halo, the upper ghost rows'
+// sums formed but not sent, nothing received: kle_mat_time_local_spmv)
+static int gsym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart, bool local = false)
 {
     kle_ctx *c = A->ctx;
     hipStream_t st = c->stream;
@@ -1770,7 +1772,7 @@ static int gsym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate
     const bool det = g_tune.spmv_sym_det != 0;
     // N > 1 with overlap: the groups that read no ghost column, then (comm
     // stream) the halo, then the rest; all RCCL calls on the comm stream
-    const bool ovl = dist && A->halo_overlap != 0;
+    const bool ovl = dist && !local && A->halo_overlap != 0;
     hipStream_t cs = ovl ? c->comm_stream : st;
     auto launch = [&](auto kern, int slot, int64_t l0, int64_t nl, int US) {
         if (nl <= 0) return;
@@ -1814,14 +1816,15 @@ static int gsym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate
             KLE_HIP(hipEventRecord(c->ev_x_ready, st));
             KLE_HIP(hipStreamWaitEvent(cs, c->ev_x_ready, 0));
         }
-        KLE_TRY(halo_exchange(c, x->base, x->ghost_lo, x->n_local, x->ghost_hi, x->lo_rank, x->hi_rank, x->send_lo,
-                              x->send_hi, cs, x->plan.get()));
+        if (!local)
+            KLE_TRY(halo_exchange(c, x->base, x->ghost_lo, x->n_local, x->ghost_hi, x->lo_rank, x->hi_rank,
+                                  x->send_lo, x->send_hi, cs, x->plan.get()));
         if (ovl) {
             KLE_HIP(hipEventRecord(c->ev_halo_done, cs));
             KLE_HIP(hipStreamWaitEvent(st, c->ev_halo_done, 0));
         }
         KLE_TRY(gbrick_launch(A, x, y, istate));
-    } else if (!dist) {
+    } else if (!dist || local) {
         KLE_TRY(tiles(0));
         KLE_TRY(tiles(1));
     } else if (ovl) {
@@ -1843,7 +1846,7 @@ static int gsym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate
     KLE_TRY(gsym_gather(A, y->d, 0, ntot, istate, dpart && !dist ? x->d : nullptr, dpart, A->sym_gbrick, st,
                         A->sym_gbrick && A->d_ssingle ? x->d : nullptr));
     KLE_HIP(hipGetLastError());
-    if (!dist) return 0;
+    if (!dist || local) return 0;
     // the upper ghost nodes' sums back to their owners, added in ascending
     // rank order of the senders (MPISBAIJ's reverse scatter)
     if (ovl) {
@@ -2446,11 +2449,12 @@ int sym_dot_parts(const kle_mat *A)
 //         touch; main: the lowest rows, + d_sgrecv last (fixed order: y stays
 //         bitwise reproducible with spmv_sym_det).
 // All RCCL calls stay on the comm stream, in the same order on every rank.
-int sym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart)
+int sym_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, double *dpart, bool local)
 {
     kle_ctx *c = A->ctx;
     hipStream_t st = c->stream;
-    if (A->sym_graph) return gsym_spmv(A, x, y, istate, dpart);
+    if (A->sym_graph) return gsym_spmv(A, x, y, istate, dpart, local);
+    if (local) return fail(KLE_ERR_SUP, "local product: graph symmetric storage only");
     if (A->sym_brick) return brick_spmv(A, x, y, istate, dpart);
     const SymGeo g = sym_geo(A);
     const int64_t ntiles = (int64_t)g.ntx * g.nty * g.ntz, n = A->nrows, Lxy = (int64_t)g.Lx * g.Ly;

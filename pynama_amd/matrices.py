@@ -63,12 +63,12 @@ class MatFS:
         builds K, Krhs and Rw as element-wise operators and assembles nothing
         (uniform box meshes, one rank or slabs on several; anything else
         raises Error 56).  "sumfac" builds them as sum-factorised operators
-        (Mat.createKLESumFactored, Mat.createRwSumFactored: any one-rank
+        (Mat.createKLESumFactored, Mat.createRwSumFactored: any
         mesh, unstructured included) and assembles nothing either; Rd is the
         empty matrix and mat.kle keeps its order.
         opType (default: -kle_op_type, default "assembled"): "element" does the
         same for Curl, SrT and DivSrT, "sumfac" with every element's own
-        geometry on any one-rank mesh (Mat.createOperatorSumFactored); with
+        geometry on any mesh, one rank or the parts of a partition (Mat.createOperatorSumFactored); with
         both, nothing at all is assembled."""
         if self.dom.getBoundaryType() != "FS":
             raise Error(56, "MatFS needs free-slip (Dirichlet) boundaries")
@@ -94,7 +94,7 @@ class MatFS:
             self.kle = [self.K, self.Krhs, self.Rw, self.Rd]
             return
         if kleType == "sumfac":
-            # matrix-free on any one-rank mesh: the operators getSumFactoredK /
+            # matrix-free on any mesh, one rank or the parts of a partition: the operators getSumFactoredK /
             # Krhs / Rw return, sharing one geometry set
             self.K, self.Krhs, self.Rw = self.getSumFactoredK(), self.getSumFactoredKrhs(), self.getSumFactoredRw()
             for m, n in ((self.K, "K"), (self.Krhs, "Krhs"), (self.Rw, "Rw")):
@@ -148,7 +148,7 @@ class MatFS:
     def getSumFactoredK(self):
         """K as a sum-factorised element-wise operator
         (Mat.createKLESumFactored): no assembled values and no element matrix,
-        any one-rank mesh (box or unstructured).  Created on first use."""
+        any mesh, one rank or the parts of a partition (box or unstructured).  Created on first use."""
         if getattr(self, "_sumfacK", None) is None:
             self._sumfacK = Mat.createKLESumFactored(self.dom.getMesh(), "K")
         return self._sumfacK
@@ -197,7 +197,7 @@ class MatNS(MatFS):
     def build(self, buildKLE=True, buildOperators=True, kleType=None, opType=None, nsType=None):
         """opType "element" or "sumfac" (default: -kle_op_type): Curl, SrT and
         DivSrT as element-wise operators, which carry no boundary rule
-        ("sumfac": any one-rank mesh; the NS matrices stay assembled).
+        ("sumfac": any mesh, one rank or the parts of a partition; the NS matrices stay assembled).
         nsType (default: -kle_ns_type, default "assembled"): "element" builds
         K, Krhs, Rw, Kfs, Krhsfs, Rwfs and K + Kfs as element-wise operators
         (Mat.createNSElement) and never calls kle_assemble_ns; Rd and Rdfs are
@@ -259,7 +259,7 @@ class Operators:
     element) nothing is assembled: the three are element-wise operators
     (Mat.createOperatorElement; uniform box meshes, one rank or slabs on
     several).  With opType "sumfac" they read every element's own geometry
-    (Mat.createOperatorSumFactored; any one-rank mesh)."""
+    (Mat.createOperatorSumFactored; any mesh, one rank or the parts of a partition)."""
 
     def __init__(self):
         self.Curl = self.SrT = self.DivSrT = None

@@ -408,16 +408,18 @@ class Mat:
 
     @classmethod
     def createKLESumFactored(cls, mesh, which="K"):
-        """Sum-factorised element-wise K or Krhs of any one-rank mesh, uniform
-        box or unstructured (kle_mat_create_kle_sumfac): the product is a
+        """Sum-factorised element-wise K or Krhs of any mesh, uniform box or
+        unstructured, on one rank or on the parts of a partition (box slabs;
+        Gmsh slab and inertial partitions; owned rows bit-identical to the
+        one-rank product) (kle_mat_create_kle_sumfac): the product is a
         quadrature-point evaluation with per-point geometry -- 1-D passes with
         the basis tables, c_q and inv J from the tables the assembly's geometry
         kernel fills -- and reads neither assembled values nor an element
         matrix.  mult, *, multAdd, createVecLeft/Right, getDiagonal, the size
         getters, getInfo, spmvKernel, timeLocalSpmv and KSP.setOperators work
         as on createKLEElement's operators; calls that need stored values and
-        copyDirichletRows raise Error 56, as do which="Rw" (createRwSumFactored), no-slip meshes,
-        several ranks and a mesh partitioned for another rank count than the
+        copyDirichletRows raise Error 56, as do which="Rw" (createRwSumFactored), no-slip meshes
+        and a mesh partitioned for another rank count than the
         context's; any other `which` raises Error 62."""
         kinds = {"K": 0, "Krhs": 1, "Rw": 2}
         if which not in kinds:
@@ -431,15 +433,15 @@ class Mat:
 
     @classmethod
     def createRwSumFactored(cls, mesh):
-        """Sum-factorised element-wise Rw [dim N x dim_w N] of any one-rank
-        mesh, uniform box or unstructured (kle_mat_create_rw_sumfac): a
+        """Sum-factorised element-wise Rw [dim N x dim_w N] of any mesh,
+        uniform box or unstructured, one rank or several (kle_mat_create_rw_sumfac): a
         quadrature-point evaluation sharing the geometry tables of
         createKLESumFactored's K and Krhs on the same mesh; Dirichlet rows are
         +0.0.  mult, *, multAdd, createVecLeft/Right, the size getters,
         getInfo, spmvKernel and timeLocalSpmv work; getDiagonal,
         copyDirichletRows and calls that need stored values raise Error 56, as
-        do no-slip meshes, several ranks and a mesh partitioned for another
-        rank count than the context's."""
+        do no-slip meshes and a mesh partitioned for another rank count than
+        the context's."""
         ctx = get_ctx()
         h = C.c_void_p()
         call("kle_mat_create_rw_sumfac", ctx.h, mesh._h, C.byref(h))
@@ -450,12 +452,12 @@ class Mat:
     @classmethod
     def createOperatorSumFactored(cls, mesh, which="Curl"):
         """Element-wise Curl, SrT or DivSrT with every element's own geometry,
-        on any one-rank mesh, uniform box or unstructured, free-slip or no-slip
-        (kle_mat_create_operator_sumfac): the products of
+        on any mesh, uniform box or unstructured, free-slip or no-slip, one
+        rank or several (kle_mat_create_operator_sumfac): the products of
         createOperatorElement with a nodal geometry table over all elements and
         a gather over a CSR incidence list (any valence).  Same call surface;
-        several ranks and a mesh partitioned for another rank count than the
-        context's raise Error 56, any other `which` Error 62."""
+        a mesh partitioned for another rank count than the context's raises
+        Error 56, any other `which` Error 62."""
         kinds = {"Curl": 0, "SrT": 1, "DivSrT": 2}
         if which not in kinds:
             raise Error(62, f"createOperatorSumFactored: which must be 'Curl', 'SrT' or 'DivSrT', not {which!r}")

@@ -57,7 +57,7 @@ class KleSolver:
         # (-kle_mat_type element) mat.K, mat.Krhs and mat.Rw are those already.
         # -kle_k_type sumfac: the KSP's operator and rhs()'s Krhs are the
         # sum-factorised operators (MatFS.getSumFactoredK / getSumFactoredKrhs:
-        # any one-rank mesh, unstructured included); Rw stays mat.Rw.
+        # any mesh, one rank or the parts of a partition, unstructured included); Rw stays mat.Rw.
         ktype = Options().getString("kle_k_type", "assembled")
         if ktype not in ("assembled", "element", "sumfac"):
             raise Error(62, f"-kle_k_type {ktype}: assembled | element | sumfac")
