@@ -12,20 +12,41 @@ namespace kle {
 // and row mirrors, then row_bcast15 / row_bcast31 carry the row sums into
 // lane 63, which every lane reads back.  Three sums at once, their steps
 // interleaved (no hazard nops between a step's add and the next step's DPP
-// read); the full-row steps use the source as the unused "old" operand
-// (every lane is written), only the row broadcasts need zeros.
+// read).
+// The "old" operand of a DPP move is tied to its destination.  The four
+// full-row steps (row and bank mask 0xF, permutations whose every source lane
+// exists) write every lane, so they take no old operand at all (mov_dpp):
+// with the source as old, as before, the source stayed live for the add and
+// the compiler copied it first -- 6 v_mov_b32 per step, 24 per row sum.
+// Every lane of their result is defined.  The two row broadcasts write rows
+// 1, 3 and rows 2, 3 only; the lanes they leave alone are added to as well
+// (and lane 63, which is read back, is a calling lane's value only there), so
+// those two keep a defined old operand, zero: their 6 zero moves cost what
+// the copies cost, and no lane of a, b, c is ever undefined.
+template <int ctrl>
+__device__ __forceinline__ int dpp_full(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, ctrl, 0xF, 0xF, false);
+}
+
 template <int ctrl, int row_mask>
 __device__ __forceinline__ void dpp3(double &a, double &b, double &c)
 {
-    constexpr bool all = row_mask == 0xF;
     const int al = __double2loint(a), ah = __double2hiint(a), bl = __double2loint(b), bh = __double2hiint(b);
     const int cl = __double2loint(c), ch = __double2hiint(c);
-    const int a2 = __builtin_amdgcn_update_dpp(all ? al : 0, al, ctrl, row_mask, 0xF, false);
-    const int a3 = __builtin_amdgcn_update_dpp(all ? ah : 0, ah, ctrl, row_mask, 0xF, false);
-    const int b2 = __builtin_amdgcn_update_dpp(all ? bl : 0, bl, ctrl, row_mask, 0xF, false);
-    const int b3 = __builtin_amdgcn_update_dpp(all ? bh : 0, bh, ctrl, row_mask, 0xF, false);
-    const int c2 = __builtin_amdgcn_update_dpp(all ? cl : 0, cl, ctrl, row_mask, 0xF, false);
-    const int c3 = __builtin_amdgcn_update_dpp(all ? ch : 0, ch, ctrl, row_mask, 0xF, false);
+    int a2, a3, b2, b3, c2, c3;
+    if constexpr (row_mask == 0xF) {
+        a2 = dpp_full<ctrl>(al), a3 = dpp_full<ctrl>(ah);
+        b2 = dpp_full<ctrl>(bl), b3 = dpp_full<ctrl>(bh);
+        c2 = dpp_full<ctrl>(cl), c3 = dpp_full<ctrl>(ch);
+    } else {
+        a2 = __builtin_amdgcn_update_dpp(0, al, ctrl, row_mask, 0xF, false);
+        a3 = __builtin_amdgcn_update_dpp(0, ah, ctrl, row_mask, 0xF, false);
+        b2 = __builtin_amdgcn_update_dpp(0, bl, ctrl, row_mask, 0xF, false);
+        b3 = __builtin_amdgcn_update_dpp(0, bh, ctrl, row_mask, 0xF, false);
+        c2 = __builtin_amdgcn_update_dpp(0, cl, ctrl, row_mask, 0xF, false);
+        c3 = __builtin_amdgcn_update_dpp(0, ch, ctrl, row_mask, 0xF, false);
+    }
     a += __hiloint2double(a3, a2);
     b += __hiloint2double(b3, b2);
     c += __hiloint2double(c3, c2);
