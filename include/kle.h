@@ -542,7 +542,8 @@ int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **o
  * paths), pipecg or gmres and PC none or jacobi.  Calls that need stored
  * values, and kle_mat_copy_dirichlet_rows, return KLE_ERR_SUP.
  * KLE_ERR_SUP also for which 2 (Rw: kle_mat_create_rw_sumfac), no-slip meshes
- * and a mesh whose nranks is not the context's; KLE_ERR_ARG for any other
+ * (their operators: kle_mat_create_ns_sumfac) and a mesh whose nranks is not
+ * the context's; KLE_ERR_ARG for any other
  * which.  Every table index is checked on the host before upload
  * (connectivity inside the ext range, incidence consistent with it and
  * ascending, the element lists disjoint, covering and true to their kind,
@@ -596,7 +597,8 @@ int kle_mat_create_kle_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **ou
  * kle_mat_spmv_kernel ("k_sumfac_rw<D>+k_sumfac_gather_rw<D>") and
  * kle_mat_time_local_spmv.  KLE_ERR_SUP: kle_mat_get_diagonal,
  * kle_mat_copy_dirichlet_rows, every call that needs stored values, no-slip
- * meshes and a mesh whose nranks is not the context's.
+ * meshes (their Rw and Rwfs: kle_mat_create_ns_sumfac) and a mesh whose nranks
+ * is not the context's.
  * kle_ksp_set_operators refuses the non-square 2-D Rw before any
  * launch.  Every table index is checked on the host before upload. */
 int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out);
@@ -636,10 +638,59 @@ int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out);
  * kle_mat_create_kle_element; ghost DoFs are masked through the ext-indexed
  * classes.  Each operator owns its tables and workspace.
  * Needs a box mesh with its no-slip DoFs set (kle_mesh_set_noslip_*).
- * KLE_ERR_SUP for an unstructured mesh, a free-slip mesh and a mesh whose
- * nranks is not the context's; KLE_ERR_ARG for a bad which.  Every index
+ * KLE_ERR_SUP for an unstructured mesh (any mesh: kle_mat_create_ns_sumfac), a
+ * free-slip mesh and a mesh whose nranks is not the context's; KLE_ERR_ARG for
+ * a bad which.  Every index
  * table entry and class is checked on the host before upload. */
 int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
+/* The same seven no-slip operators (which 0 K, 1 Krhs, 2 Rw, 3 Kfs, 4 Krhsfs,
+ * 5 Rwfs, 6 K + Kfs) sum-factorised, on any mesh, kind 0 (box) or kind 1
+ * (unstructured), 2-D or 3-D, ngl 2..8, one rank or the parts of a partition:
+ * the table of passes and row rules above, unchanged, with the
+ * quadrature-point kernels of kle_mat_create_kle_sumfac /
+ * kle_mat_create_rw_sumfac as the pass instead of the element GEMM.  No
+ * stored values and no element matrix.
+ * The mask is per DoF, so the connectivity stays unmasked and each K-family
+ * operator carries a class table [E][nn] of one byte per element node: the dim
+ * classes of that node at 2 bits each, taken from the ext-indexed classes of
+ * the mesh (ghost DoFs included).  A pass is one launch of
+ * k_sumfac_elem<D, LIST, CLS = true> whose argument is the 3-bit set of kept
+ * classes: component b of a site loads x iff (keep >> cls_b) & 1, else it is 0
+ * and x is never read there.  The CLS = false instantiations are the free-slip
+ * kernels, instruction for instruction.  Rw and Rwfs keep every vorticity
+ * column and run k_sumfac_rw unchanged.  Kfs runs two passes, {F,T} -> {T}
+ * and {T} -> {F}, into two result arrays.  k_sumfac_gather_cls, one thread per
+ * owned DoF, applies the rule of the row's class: a summed row adds its node's
+ * entries of its pass's result array over the CSR incidence list in ascending
+ * element order (Kfs's T rows then add -x_i), an identity row returns x_i bit
+ * for bit, a zero row is +0.0 and reads nothing.  No atomics: the same input
+ * gives the same bits.  K + Kfs forms the element sums (at most eps S |x_i|
+ * per row from the assembled 1 + (S - 1)).
+ * kle_mat_get_diagonal: formed once at creation by k_sumfac_diag and a gather
+ * by class -- the element diagonal sums on the summed rows of K and K + Kfs,
+ * those sums - 1 on Kfs's T rows, 1 on identity rows, 0 elsewhere; refused for
+ * Rw and Rwfs.  kle_mat_copy_dirichlet_rows copies the identity rows.
+ * The geometry tables are the mesh's shared, reference-counted set: the seven
+ * operators of one mesh (and its free-slip-form collocation operators at
+ * ngl > 3) hold one set.  Each operator owns its connectivity, incidence
+ * list, class table, class bytes of the owned DoFs and result arrays.
+ * Several ranks: the ext-local connectivity and the inner / outer element
+ * lists of kle_mat_create_kle_sumfac; one forward halo of x per product
+ * (Kfs's two passes share it, both run per list); owned rows bit-identical to
+ * the one-rank product.
+ * Call surface as kle_mat_create_ns_element: kle_mat_mult, kle_mat_mult_add,
+ * kle_mat_get_diagonal, the size and ownership getters, kle_mat_get_info
+ * (nz_used 0), kle_mat_time_local_spmv, kle_mat_spmv_kernel
+ * ("k_sumfac_elem<D,cls>[x2]+k_sumfac_gather_cls<D>", Rw and Rwfs
+ * "k_sumfac_rw<D>+k_sumfac_gather_cls<D>"), kle_mat_spmv_bytes (the class
+ * table and one result array per pass counted) and kle_ksp_set_operators on
+ * K and K + Kfs with cg (classic and single reduction), pipecg or gmres and PC
+ * none or jacobi.  Calls that need stored values return KLE_ERR_SUP.
+ * Needs a mesh with its no-slip DoFs set (kle_mesh_set_noslip_*).  KLE_ERR_SUP
+ * for a free-slip mesh and a mesh whose nranks is not the context's;
+ * KLE_ERR_ARG for a bad which.  Connectivity, incidence, element lists and
+ * every class are checked on the host before upload. */
+int kle_mat_create_ns_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out);
 /* Element-wise collocation operator of a uniform box mesh: which 0 Curl
  * [dim_w N x dim N], 1 SrT [dim_s N x dim N], 2 DivSrT [dim N x dim_s N], the
  * operators kle_assemble_operators assembles, with no stored values:

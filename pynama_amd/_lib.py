@@ -129,6 +129,7 @@ _SIGS = {
     "kle_assemble_ns": [vp, vp] + [pvp] * 9,
     "kle_mat_create_kle_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_ns_element": [vp, vp, C.c_int, pvp],
+    "kle_mat_create_ns_sumfac": [vp, vp, C.c_int, pvp],
     "kle_mat_create_operator_element": [vp, vp, C.c_int, pvp],
     "kle_mat_create_kle_sumfac": [vp, vp, C.c_int, pvp],
     "kle_mat_create_rw_sumfac": [vp, vp, pvp],

@@ -59,7 +59,7 @@
 // DoF -- classes F / T / N from the mesh's dof_cls -- instead of per node, and
 // Kfs's kept columns depend on the row's class.  Each is at most two passes of
 // (column classes kept -> row classes taking the sum) and a fixed rule on every
-// other row (NS_SPECS below):
+// other row (NS_SPECS, kle_internal.hpp):
 //
 //   k_elem_gemm<CW, NCT, DOF = true>  the same kernel with its column index
 //                  from a per-element, per-column table [E][nc] of ext-local x
@@ -102,9 +102,6 @@ struct ElemOp {
     unsigned rules = 0;         // row rule of class c in byte c (NS_*)
     unsigned drules = 0;        // diagonal of class c in byte c: 0 zero, 1 one, 2 the element sums, 3 the sums - 1
 };
-
-// row rule of a DoF class: what the class gather writes
-enum : unsigned { NS_ZERO = 0, NS_IDENT = 1, NS_SUM0 = 2, NS_SUM1 = 3, NS_KIND = 3, NS_MINUS_X = 4 };
 
 constexpr int EG_KC = 64;            // k rows of X per LDS chunk
 constexpr int EG_TR = 2;             // 16-row tiles per wave
@@ -759,6 +756,7 @@ using namespace kle;
 extern "C" int kle_mat_copy_dirichlet_rows(const kle_mat *A, const kle_vec *src, kle_vec *dst)
 {
     KLE_ARG(A && src && dst, "null arg");
+    if (A->kind == 2 && A->sumfac) return sumfac_copy_ident_rows(A, src, dst);
     if (A->kind != 2 || !A->elem)
         return fail(KLE_ERR_SUP, "copyDirichletRows: an element-wise operator only (it holds the Dirichlet flags)");
     const ElemOp *P = A->elem;
@@ -844,28 +842,7 @@ extern "C" int kle_mat_create_kle_element(kle_ctx *ctx, kle_mesh *m, int which, 
 }
 
 // The no-slip operators of MatNS.buildNS (mat_ns.py:47-145) in element-wise
-// form.  Every one is S_e^T K_e0 S_e (Rw, Rwfs: S_e^T Rw_e0 S_e^w) restricted
-// to at most two passes of (column classes kept -> row classes taking the sum),
-// with a fixed rule on every other row; classes F / T / N per velocity DoF.
-namespace {
-struct NsSpec {
-    bool rw, negate;
-    int npass;
-    unsigned cols[2];   // column classes pass p keeps (bit c = class c); Rw, Rwfs: every w column
-    unsigned rule[3];   // row rule of F, T, N
-};
-constexpr unsigned CF = 1u << DOF_FREE, CT = 1u << DOF_TANG, CN = 1u << DOF_NORMAL;
-const NsSpec NS_SPECS[7] = {
-    /* K      */ {false, false, 1, {CF, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
-    /* Krhs   */ {false, true, 1, {CT | CN, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
-    /* Rw     */ {true, false, 1, {0, 0}, {NS_SUM0, NS_ZERO, NS_ZERO}},
-    /* Kfs    */ {false, false, 2, {CF | CT, CT}, {NS_SUM1, NS_SUM0 | NS_MINUS_X, NS_ZERO}},
-    /* Krhsfs */ {false, true, 1, {CN, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
-    /* Rwfs   */ {true, false, 1, {0, 0}, {NS_ZERO, NS_SUM0, NS_ZERO}},
-    /* K+Kfs  */ {false, false, 1, {CF | CT, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
-};
-}  // namespace
-
+// form: NS_SPECS (kle_internal.hpp) with the element GEMM as the pass.
 extern "C" int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
 {
     KLE_ARG(ctx && m && out, "null arg");
@@ -935,14 +912,7 @@ extern "C" int kle_mat_create_ns_element(kle_ctx *ctx, kle_mesh *m, int which, k
     P->maxinc = maxinc;
     P->E = E;
     P->N = N;
-    for (int c = 0; c < 3; ++c) {
-        const unsigned r = S.rule[c], kind = r & NS_KIND;
-        P->rules |= r << (8 * c);
-        // the diagonal: a summed row holds its own column where its pass keeps the row's class
-        unsigned d = kind == NS_IDENT ? 1u : 0u;
-        if (kind >= NS_SUM0 && !S.rw && ((S.cols[kind - NS_SUM0] >> c) & 1u)) d = r & NS_MINUS_X ? 3u : 2u;
-        P->drules |= d << (8 * c);
-    }
+    ns_rule_words(S, &P->rules, &P->drules);
     // (element columns per held operand and the ghost layer's row groups: as kle_mat_create_kle_element)
     const int64_t nrg = (ndp + EG_ROWS - 1) / EG_ROWS;
     P->rg_top = (nd - nd / m->ngl) / EG_ROWS;

@@ -498,6 +498,7 @@ int mesh_geometry(kle_ctx *ctx, kle_mesh *m, bool kle, bool ops, std::shared_ptr
 // sum-factorised K, Krhs and Rw (kle_sumfac.hip; kle_mat kind 2 with sumfac set)
 int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, bool local = false);
 int sumfac_diagonal(const kle_mat *A, kle_vec *d);
+int sumfac_copy_ident_rows(const kle_mat *A, const kle_vec *src, kle_vec *dst);  // (no-slip operators only)
 void sumfac_drop(kle_mat *A);
 double sumfac_spmv_bytes(const kle_mat *A);
 std::string sumfac_kernel_name(const kle_mat *A);
@@ -671,6 +672,42 @@ int pattern_csr(const kle_mesh *m, int which, std::vector<int64_t> &row_ptr, std
 // row i (nodes sharing a local cell); on_face: Face Sets bits of an ext node.
 void umesh_row_nodes(const kle_mesh *m, int64_t i, std::vector<int64_t> &out);
 enum DofClass : uint8_t { DOF_FREE = 0, DOF_TANG = 1, DOF_NORMAL = 2 };
+// The no-slip operators of MatNS.buildNS (mat_ns.py:47-145) without stored
+// values (kle_elem.hip, kle_sumfac.hip).  Every one is the free-slip element
+// sum restricted to at most two passes of (column classes kept -> row classes
+// taking the sum), with a fixed rule on every other row; classes F / T / N per
+// velocity DoF.  Row rule of a DoF class, what the class gather writes:
+enum : unsigned { NS_ZERO = 0, NS_IDENT = 1, NS_SUM0 = 2, NS_SUM1 = 3, NS_KIND = 3, NS_MINUS_X = 4 };
+struct NsSpec {
+    bool rw, negate;
+    int npass;
+    unsigned cols[2];   // column classes pass p keeps (bit c = class c); Rw, Rwfs: every w column
+    unsigned rule[3];   // row rule of F, T, N
+};
+constexpr unsigned NS_CF = 1u << DOF_FREE, NS_CT = 1u << DOF_TANG, NS_CN = 1u << DOF_NORMAL;
+constexpr NsSpec NS_SPECS[7] = {
+    /* K      */ {false, false, 1, {NS_CF, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
+    /* Krhs   */ {false, true, 1, {NS_CT | NS_CN, 0}, {NS_SUM0, NS_IDENT, NS_IDENT}},
+    /* Rw     */ {true, false, 1, {0, 0}, {NS_SUM0, NS_ZERO, NS_ZERO}},
+    /* Kfs    */ {false, false, 2, {NS_CF | NS_CT, NS_CT}, {NS_SUM1, NS_SUM0 | NS_MINUS_X, NS_ZERO}},
+    /* Krhsfs */ {false, true, 1, {NS_CN, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
+    /* Rwfs   */ {true, false, 1, {0, 0}, {NS_ZERO, NS_SUM0, NS_ZERO}},
+    /* K+Kfs  */ {false, false, 1, {NS_CF | NS_CT, 0}, {NS_SUM0, NS_SUM0, NS_IDENT}},
+};
+// the diagonal of class c in byte c: 0 zero, 1 one (identity rows), 2 the
+// element diagonal sums (a summed row whose pass keeps the row's own class),
+// 3 those sums - 1 (Kfs's tangential rows)
+inline void ns_rule_words(const NsSpec &S, unsigned *rules, unsigned *drules)
+{
+    *rules = *drules = 0;
+    for (int c = 0; c < 3; ++c) {
+        const unsigned r = S.rule[c], kind = r & NS_KIND;
+        *rules |= r << (8 * c);
+        unsigned d = kind == NS_IDENT ? 1u : 0u;
+        if (kind >= NS_SUM0 && !S.rw && ((S.cols[kind - NS_SUM0] >> c) & 1u)) d = r & NS_MINUS_X ? 3u : 2u;
+        *drules |= d << (8 * c);
+    }
+}
 // which PETSc entries of a node block exist (MatNS.buildNS, mat_ns.py:47-145)
 enum MaskRule { MASK_NONE = 0, MASK_KFS = 1, MASK_KRHSFS = 2, MASK_TANG_ROWS = 3, MASK_KSUM = 4 };
 __host__ __device__ inline bool mask_entry(int rule, int rc, int cc, bool diag)

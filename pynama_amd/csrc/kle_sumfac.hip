@@ -79,6 +79,30 @@
 // (elem_ranges over list positions: el_ghost 0, el_int1 the inner list's length).  ws, the geometry tables and conn stay indexed by the element's
 // own id, so the gather sums a node's entries in the one-rank order: the owned
 // rows are the one-rank product's bit for bit.
+//
+// No-slip meshes (kle_mat_create_ns_sumfac): the seven matrices of
+// MatNS.buildNS are the same sums with masks per velocity DoF -- classes F / T
+// / N from the mesh's dof_cls -- each at most two passes of (column classes
+// kept -> row classes taking the sum) and a fixed rule on every other row
+// (NS_SPECS, kle_internal.hpp; the table of kle_elem.hip):
+//
+//   k_sumfac_elem<DIM, LIST, CLS = true>  the same kernel with conn unmasked
+//       and a class table [E][nn], one byte per element node holding the dim
+//       classes of its DoFs at 2 bits each (ext-indexed, ghosts included);
+//       the pass's 3-bit set of kept classes is a launch argument and
+//       component b of a site loads x iff it holds the DoF's class.  Kfs runs
+//       two passes into two result arrays; Rw and Rwfs keep every column and
+//       run k_sumfac_rw unchanged.  The CLS = false instantiations are the
+//       free-slip kernels, instruction for instruction.
+//   k_sumfac_gather_cls  one thread per owned DoF; the rule byte of its class
+//       says zero (+0.0, nothing read), identity (x_i bit for bit), the sum
+//       from pass 0 or from pass 1 over the CSR incidence list (ascending
+//       element, no atomics) and whether -x_i is added (Kfs's T rows).
+//   k_sumfac_diag_gather_cls  the diagonal by class, once at creation, from
+//       k_sumfac_diag's element entries.
+//
+// On several ranks both passes of Kfs run per element list, so they share the
+// product's one halo.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -112,18 +136,33 @@ struct SumfacOp {
     // several ranks: the local elements as two lists, [0, n_inner) those reading
     // owned nodes alone, [n_inner, E) those reading a ghost; each ascending
     int32_t *d_elist = nullptr;  // [E] (one rank: none, the kernels take every element in order)
+    // no-slip operators (kle_mat_create_ns_sumfac): masks per velocity DoF.  which
+    // stays the kernel family (0: k_sumfac_elem, 2: k_sumfac_rw), ns_which the operator
+    int ns = 0, ns_which = 0;   // ns 1: rows by DoF class (k_sumfac_gather_cls); ns_which 0 .. 6 (NS_SPECS)
+    int npass = 1;              // element passes (Kfs: 2), pass p keeps the classes keep[p], into d_wsp[p]
+    unsigned keep[2] = {0, 0};
+    unsigned rules = 0, drules = 0;  // row rule and diagonal of class c in byte c (ns_rule_words)
+    uint8_t *d_ncls = nullptr;  // [E][nn] the dim classes of an element node, 2 bits each (K-family operators)
+    uint8_t *d_cls = nullptr;   // [N dim] class of the owned DoFs
+    double *d_wsp[2] = {nullptr, nullptr};  // [E][nn][dim] per pass (d_wsp[0] == d_ws)
 };
 
 // LIST: the batch's elements are elist[e0 .. e0 + neb) of the E listed (several
 // ranks: the inner or the outer list); conn, geo and ws stay indexed by the
 // element's own id, the LDS tile by its place in the batch
-template <int DIM, bool LIST = false>
+//
+// CLS (the no-slip operators): the mask acts per velocity
+// DoF, so conn stays unmasked and ncls [E][nn] holds the dim classes of every
+// element node at 2 bits each; component b of a site loads x iff keep, the
+// pass's 3-bit set of kept classes, holds its class.
+template <int DIM, bool LIST = false, bool CLS = false>
 __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, int sy, int sz, int se, int64_t E,
                                                      int negate, const double *__restrict__ tab,
                                                      const double *__restrict__ geoF, const double *__restrict__ geoR,
                                                      const int32_t *__restrict__ conn, const double *__restrict__ x,
                                                      double *__restrict__ ws, const int *__restrict__ istate,
-                                                     const int32_t *__restrict__ elist)
+                                                     const int32_t *__restrict__ elist,
+                                                     const uint8_t *__restrict__ ncls, unsigned keep)
 {
     if (istate && istate[I_REASON] != 0) return;
     constexpr int NIT = DIM == 3 ? 2 : 1;  // sites per thread: 512 at ngl 8 in 3-D
@@ -161,10 +200,16 @@ __global__ __launch_bounds__(256) void k_sumfac_elem(int ngl, int nn, int neb, i
         base[it] = el * se + sk[it] * sz + sj[it] * sy + si[it];
         if (ok[it]) {
             const int node = conn[LIST ? eid[it] * nn + l : t0 + t];
+            unsigned cb = 0;
+            if constexpr (CLS) cb = ncls[LIST ? eid[it] * nn + l : t0 + t];
 #pragma unroll
             for (int b = 0; b < DIM; ++b) {
                 double v = 0.0;
-                if (node >= 0) v = x[(int64_t)node * DIM + b];  // (a dropped entry is never read)
+                if constexpr (CLS) {
+                    if ((keep >> ((cb >> (2 * b)) & 3u)) & 1u) v = x[(int64_t)node * DIM + b];
+                } else {
+                    if (node >= 0) v = x[(int64_t)node * DIM + b];  // (a dropped entry is never read)
+                }
                 sx[b * SC + base[it]] = v;
             }
         }
@@ -856,6 +901,78 @@ __global__ __launch_bounds__(256) void k_sumfac_diag_gather(int64_t N, int which
     d[i] = s;
 }
 
+// No-slip operators: one thread per owned DoF, its row by the rule byte of its
+// class (as k_elem_gather_cls) -- zero (+0.0, nothing read), the identity (x_i
+// bit for bit) or the sum of its node's incidence entries from the element
+// results of pass 0 or pass 1, ascending element; NS_MINUS_X adds -x_i (the -1
+// on Kfs's tangential diagonal).  x is null where the column space is the
+// vorticity's (Rw, Rwfs: no rule of theirs reads it).
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_gather_cls(int64_t N, unsigned rules,
+                                                           const int32_t *__restrict__ incp,
+                                                           const int32_t *__restrict__ inc,
+                                                           const uint8_t *__restrict__ cls,
+                                                           const double *__restrict__ ws0,
+                                                           const double *__restrict__ ws1,
+                                                           const double *__restrict__ x, double *__restrict__ y,
+                                                           const int *__restrict__ istate)
+{
+    if (istate && istate[I_REASON] != 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const unsigned r = (rules >> (8 * cls[i])) & 0xffu, kind = r & NS_KIND;
+    if (kind == NS_ZERO) {
+        y[i] = 0.0;
+        return;
+    }
+    if (kind == NS_IDENT) {
+        y[i] = x[i];
+        return;
+    }
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    const double *__restrict__ ws = kind == NS_SUM0 ? ws0 : ws1;
+    double s = 0.0;
+    const int j1 = incp[node + 1];
+    for (int j = incp[node]; j < j1; ++j) s += ws[(int64_t)inc[j] * DIM + a];
+    if (r & NS_MINUS_X) s += -x[i];
+    y[i] = s;
+}
+
+// diagonal by class: 0, 1 (identity rows), the incident elements' diagonal
+// entries in gather order, those sums + (-1) (Kfs's tangential rows)
+template <int DIM>
+__global__ __launch_bounds__(256) void k_sumfac_diag_gather_cls(int64_t N, unsigned drules,
+                                                                const int32_t *__restrict__ incp,
+                                                                const int32_t *__restrict__ inc,
+                                                                const uint8_t *__restrict__ cls,
+                                                                const double *__restrict__ ws, double *__restrict__ d)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * DIM) return;
+    const unsigned r = (drules >> (8 * cls[i])) & 0xffu;
+    if (r < 2) {
+        d[i] = r ? 1.0 : 0.0;
+        return;
+    }
+    const int64_t node = i / DIM;
+    const int a = (int)(i - node * DIM);
+    double s = 0.0;
+    const int j1 = incp[node + 1];
+    for (int j = incp[node]; j < j1; ++j) s += ws[(int64_t)inc[j] * DIM + a];
+    d[i] = r == 3 ? s + (-1.0) : s;
+}
+
+// dst_i = src_i on the identity rows of a no-slip operator, nothing else touched
+__global__ __launch_bounds__(256) void k_sumfac_copy_ident_cls(int64_t n, unsigned rules,
+                                                               const uint8_t *__restrict__ cls,
+                                                               const double *__restrict__ src, double *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (((rules >> (8 * cls[i])) & NS_KIND) == NS_IDENT) dst[i] = src[i];
+}
+
 // the element kernel over every element in order (list null: one rank), or
 // over the n elements list names
 template <int DIM>
@@ -868,10 +985,15 @@ static void launch_sumfac_elems(const SumfacOp *P, hipStream_t st, const int32_t
         if (P->which == 2)                                                                                            \
             hipLaunchKernelGGL((k_sumfac_rw<DIM, LIST>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,    \
                                P->sz, P->se, n, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws, istate, list); \
+        else if (P->ns) /* a pass per kept class set, each into its own result array (Kfs: two) */                    \
+            for (int p = 0; p < P->npass; ++p)                                                                        \
+                hipLaunchKernelGGL((k_sumfac_elem<DIM, LIST, true>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn,       \
+                                   P->neb, P->sy, P->sz, P->se, n, P->negate, P->d_tab, P->d_geoF, P->d_geoR,         \
+                                   P->d_conn, x, P->d_wsp[p], istate, list, P->d_ncls, P->keep[p]);                   \
         else                                                                                                          \
             hipLaunchKernelGGL((k_sumfac_elem<DIM, LIST>), dim3(ge), dim3(256), 0, st, P->ngl, P->nn, P->neb, P->sy,  \
                                P->sz, P->se, n, P->negate, P->d_tab, P->d_geoF, P->d_geoR, P->d_conn, x, P->d_ws,     \
-                               istate, list);                                                                         \
+                               istate, list, nullptr, 0u);                                                            \
     } while (0)
     if (list) KLE_SUMFAC_ELEMS(true);
     else KLE_SUMFAC_ELEMS(false);
@@ -883,7 +1005,10 @@ template <int DIM>
 static void launch_sumfac_gather(const SumfacOp *P, hipStream_t st, const double *x, double *y, const int *istate)
 {
     const unsigned gn = (unsigned)((P->N * DIM + 255) / 256);
-    if (P->which == 2)
+    if (P->ns)  // (Rw, Rwfs: x is the vorticity -- their rules, zero and sum, never read it)
+        hipLaunchKernelGGL(k_sumfac_gather_cls<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->rules, P->d_incp, P->d_inc,
+                           P->d_cls, P->d_wsp[0], P->d_wsp[1], P->which == 2 ? nullptr : x, y, istate);
+    else if (P->which == 2)
         hipLaunchKernelGGL(k_sumfac_gather_rw<DIM>, dim3(gn), dim3(256), 0, st, P->N, P->d_incp, P->d_inc, P->d_dir,
                            P->d_ws, y, istate);
     else
@@ -917,11 +1042,28 @@ int sumfac_spmv(kle_mat *A, const kle_vec *x, kle_vec *y, const int *istate, boo
 int sumfac_diagonal(const kle_mat *A, kle_vec *d)
 {
     const SumfacOp *P = A->sumfac;
-    if (P && P->which == 2) return fail(KLE_ERR_SUP, "getDiagonal: the sum-factorised Rw is rectangular");
+    if (P && P->which == 2) return fail(KLE_ERR_SUP, "getDiagonal: the sum-factorised Rw is rectangular");  // (Rwfs too)
     if (!P || !P->d_diag) return fail(KLE_ERR_STATE, "sum-factorised operator without tables");
     hipStream_t st = A->ctx->stream;
     KLE_HIP(hipMemcpyAsync(d->d, P->d_diag, sizeof(double) * (size_t)P->N * P->dim, hipMemcpyDeviceToDevice, st));
     KLE_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// dst_i = src_i on the identity rows of a no-slip operator (the free-slip
+// operators refuse: kle_mat_copy_dirichlet_rows)
+int sumfac_copy_ident_rows(const kle_mat *A, const kle_vec *src, kle_vec *dst)
+{
+    const SumfacOp *P = A->sumfac;
+    if (!P || !P->ns)
+        return fail(KLE_ERR_SUP, "copyDirichletRows: an element-wise operator only (it holds the Dirichlet flags)");
+    const int64_t n = P->N * P->dim;
+    if (src->n_local != n || dst->n_local != n)
+        return fail(KLE_ERR_SIZ, "copyDirichletRows: vectors do not match the operator's rows");
+    if (src->d == dst->d) return 0;
+    hipLaunchKernelGGL(k_sumfac_copy_ident_cls, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, A->ctx->stream, n,
+                       P->rules, P->d_cls, src->d, dst->d);
+    KLE_HIP(hipGetLastError());
     return 0;
 }
 
@@ -937,6 +1079,9 @@ void sumfac_drop(kle_mat *A)
     (void)hipFree(P->d_inc);
     (void)hipFree(P->d_dir);
     (void)hipFree(P->d_elist);
+    (void)hipFree(P->d_ncls);
+    (void)hipFree(P->d_cls);
+    (void)hipFree(P->d_wsp[1]);  // (d_wsp[0] is d_ws)
     delete P;
     A->sumfac = nullptr;
 }
@@ -949,12 +1094,22 @@ static int64_t sf_ipow(int b, int d) { return d == 2 ? (int64_t)b * b : (int64_t
 // incidence list (4 (N + 1) + 4 E nn), the Dirichlet flags (N), the element
 // results read, y written (8 m).  Rw: the same streams with its own n.
 // Several ranks: E the local elements, n the ext range of x, N the owned
-// nodes, and the two element lists (4 E).
+// nodes, and the two element lists (4 E).  A no-slip operator: every
+// element-kernel stream once per pass, the class table with it (E nn bytes per
+// pass, K-family operators), one result array per pass written and read, and
+// the owned DoFs' class bytes (N dim) instead of the Dirichlet flags.
 double sumfac_spmv_bytes(const kle_mat *A)
 {
     const SumfacOp *P = A->sumfac;
     if (!P) return 0.0;
     const double nq = (double)(sf_ipow(P->npF, P->dim) + sf_ipow(P->npR, P->dim));
+    if (P->ns) {
+        const double elem = 4.0 * P->E * P->nn + (P->d_ncls ? 1.0 * P->E * P->nn : 0.0) +
+                            8.0 * P->E * nq * (1 + P->dim * P->dim) + 8.0 * 4 * P->ngl * P->ngl +
+                            8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 2.0 * 8.0 * P->E * P->nn * P->dim +
+                            (P->d_elist ? 4.0 * P->E : 0.0);
+        return P->npass * elem + 4.0 * (P->N + 1) + 4.0 * P->ninc + 1.0 * P->N * P->dim + 8.0 * A->m_local;
+    }
     return 4.0 * P->E * P->nn + 8.0 * P->E * nq * (1 + P->dim * P->dim) + 8.0 * 4 * P->ngl * P->ngl +
            8.0 * (A->n_local + A->ghost_lo + A->ghost_hi) + 2.0 * 8.0 * P->E * P->nn * P->dim + 4.0 * (P->N + 1) +
            4.0 * P->ninc + 1.0 * P->N + 8.0 * A->m_local + (P->d_elist ? 4.0 * P->E : 0.0);
@@ -965,6 +1120,9 @@ std::string sumfac_kernel_name(const kle_mat *A)
     const SumfacOp *P = A->sumfac;
     if (!P) return "?";
     const std::string d = std::to_string(P->dim);
+    if (P->ns)
+        return (P->which == 2 ? "k_sumfac_rw<" + d + ">" : "k_sumfac_elem<" + d + ",cls>" + (P->npass == 2 ? "x2" : "")) +
+               "+k_sumfac_gather_cls<" + d + ">";
     if (P->which == 2) return "k_sumfac_rw<" + d + ">+k_sumfac_gather_rw<" + d + ">";
     return "k_sumfac_elem<" + d + ">+k_sumfac_gather<" + d + ">";
 }
@@ -1103,26 +1261,50 @@ int sumfac_tables(const kle_ctx *ctx, const kle_mesh *m, int bw, ElemLayout *Lou
 
 using namespace kle;
 
-// which: 0 K, 1 Krhs, 2 Rw
-static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+// which: 0 K, 1 Krhs, 2 Rw of a free-slip mesh (ns < 0); ns 0 .. 6: the no-slip
+// operator NS_SPECS[ns] of a mesh with its DoF classes, which its kernel
+// family (0: k_sumfac_elem with the class table, 2: k_sumfac_rw)
+static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out, int ns = -1)
 {
-    if (!m->dof_cls.empty()) return fail(KLE_ERR_SUP, "sum-factorised operator: no-slip meshes are not supported");
+    const NsSpec *S = ns >= 0 ? &NS_SPECS[ns] : nullptr;
+    if (!S && !m->dof_cls.empty())
+        return fail(KLE_ERR_SUP, "sum-factorised operator: a no-slip mesh (its operators: kle_mat_create_ns_sumfac)");
+    if (S && m->dof_cls.empty())
+        return fail(KLE_ERR_SUP, "sum-factorised no-slip operator: the mesh has no no-slip DoFs (kle_mesh_set_noslip_*)");
     const int dim = m->dim, ngl = m->ngl, nn = m->nn();
     KLE_ARG((dim == 2 || dim == 3) && ngl >= 2 && ngl <= 8, "sum-factorised operator: dim 2 or 3, ngl 2..8");
     // tables (host) in ext-local ids, validated before upload
     ElemLayout L;
     std::vector<int32_t> conn, incp, inc, elist;
     KLE_TRY(sumfac_tables(ctx, m, dim, &L, conn, incp, inc, elist));
-    KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
     const int64_t E = L.E, N = L.N;
-    if ((int64_t)m->dir.size() != L.next)
-        return fail(KLE_ERR_SIZ, "sum-factorised operator: Dirichlet flags do not match the mesh");
-    // the mask rule folded into the connectivity the element kernel reads: K
-    // drops the Dirichlet entries of x (ghosts included: m->dir covers the ext
-    // range), Krhs the free ones
-    // (Rw drops nothing)
-    for (int64_t k = 0; k < E * nn && which != 2; ++k)
-        if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
+    std::vector<uint8_t> ncls;
+    if (S) {
+        if ((int64_t)m->dof_cls.size() != L.next * dim)
+            return fail(KLE_ERR_SIZ, "sum-factorised operator: DoF classes do not cover the mesh's ext range");
+        for (size_t k = 0; k < m->dof_cls.size(); ++k)
+            if (m->dof_cls[k] > DOF_NORMAL)
+                return fail(KLE_ERR_OUTOFRANGE, "sum-factorised operator: DoF %lld has the unknown class %d",
+                            (long long)k, (int)m->dof_cls[k]);
+        // the mask acts per DoF: conn stays unmasked (sumfac_tables checked it
+        // against the ext range the classes cover) and every element node
+        // carries the classes of its dim DoFs, ghosts included, 2 bits each
+        if (!S->rw) {
+            ncls.assign((size_t)E * nn, 0);
+            for (int64_t k = 0; k < E * nn; ++k)
+                for (int b = 0; b < dim; ++b) ncls[k] |= (uint8_t)(m->dof_cls[(int64_t)conn[k] * dim + b] << (2 * b));
+        }
+    } else {
+        KLE_ARG(m->dir_set, "Dirichlet nodes not set (kle_mesh_set_dirichlet_*)");
+        if ((int64_t)m->dir.size() != L.next)
+            return fail(KLE_ERR_SIZ, "sum-factorised operator: Dirichlet flags do not match the mesh");
+        // the mask rule folded into the connectivity the element kernel reads: K
+        // drops the Dirichlet entries of x (ghosts included: m->dir covers the ext
+        // range), Krhs the free ones
+        // (Rw drops nothing)
+        for (int64_t k = 0; k < E * nn && which != 2; ++k)
+            if ((m->dir[conn[k]] != 0) != (which == 1)) conn[k] = -1;
+    }
 
     // LDS layout: odd strides (in doubles) of the y lines, z planes and elements
     // (a workgroup's only element needs no element stride), as kle_colloc.hip
@@ -1150,7 +1332,15 @@ static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
     A->sumfac = P;
     elem_mat_fields(A, m, L, dim, which == 2 ? (dim == 2 ? 1 : 3) : dim);
     P->which = which;
-    P->negate = which == 1;
+    P->negate = S ? S->negate : which == 1;
+    if (S) {
+        P->ns = 1;
+        P->ns_which = ns;
+        P->npass = S->npass;
+        P->keep[0] = S->cols[0];
+        P->keep[1] = S->cols[1];
+        ns_rule_words(*S, &P->rules, &P->drules);
+    }
     P->dim = dim;
     P->ngl = ngl;
     P->nn = nn;
@@ -1187,11 +1377,38 @@ static int sumfac_create(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
     if (!rc) rc = up(&P->d_conn, conn.data(), sizeof(int32_t) * conn.size());
     if (!rc) rc = up(&P->d_incp, incp.data(), sizeof(int32_t) * incp.size());
     if (!rc) rc = up(&P->d_inc, inc.data(), sizeof(int32_t) * inc.size());
-    if (!rc) rc = up(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
+    if (!rc && !S) rc = up(&P->d_dir, m->dir.data() + L.own0, (size_t)N);
+    if (!rc && S) rc = up(&P->d_cls, m->dof_cls.data() + L.own0 * dim, (size_t)N * dim);
+    if (!rc && !ncls.empty()) rc = up(&P->d_ncls, ncls.data(), ncls.size());
     if (!rc && !elist.empty()) rc = up(&P->d_elist, elist.data(), sizeof(int32_t) * elist.size());
     if (!rc) rc = up(&P->d_ws, nullptr, sizeof(double) * (size_t)E * nn * dim);
+    P->d_wsp[0] = P->d_ws;
+    if (!rc && P->npass == 2) rc = up(&P->d_wsp[1], nullptr, sizeof(double) * (size_t)E * nn * dim);
     if (!rc && which != 2) rc = up(&P->d_diag, nullptr, sizeof(double) * (size_t)N * dim);
-    if (!rc && which != 2) {
+    if (!rc && S && which != 2) {
+        // the diagonal by class, once: the element entries into ws where a class
+        // sums them (K, Kfs, K + Kfs), gathered like a product
+        const unsigned ge = (unsigned)((E * nn + 255) / 256), gn = (unsigned)((N * dim + 255) / 256);
+        const bool sums = ((P->drules | (P->drules >> 8) | (P->drules >> 16)) & 2u) != 0;
+        hipStream_t st = ctx->stream;
+        if (dim == 2) {
+            if (sums)
+                hipLaunchKernelGGL(k_sumfac_diag<2>, dim3(ge), dim3(256), 0, st, ngl, nn, E, P->d_tab, P->d_geoF,
+                                   P->d_geoR, P->d_ws);
+            hipLaunchKernelGGL(k_sumfac_diag_gather_cls<2>, dim3(gn), dim3(256), 0, st, N, P->drules, P->d_incp,
+                               P->d_inc, P->d_cls, P->d_ws, P->d_diag);
+        } else {
+            if (sums)
+                hipLaunchKernelGGL(k_sumfac_diag<3>, dim3(ge), dim3(256), 0, st, ngl, nn, E, P->d_tab, P->d_geoF,
+                                   P->d_geoR, P->d_ws);
+            hipLaunchKernelGGL(k_sumfac_diag_gather_cls<3>, dim3(gn), dim3(256), 0, st, N, P->drules, P->d_incp,
+                               P->d_inc, P->d_cls, P->d_ws, P->d_diag);
+        }
+        hipError_t he = hipGetLastError();
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he != hipSuccess) rc = fail(KLE_ERR_DEVICE, "sum-factorised operator: diagonal kernels: %s", hipGetErrorString(he));
+    }
+    if (!rc && !S && which != 2) {
         // the diagonal, once: element entries into ws, gathered like a product
         const unsigned ge = (unsigned)((E * nn + 255) / 256), gn = (unsigned)((N * dim + 255) / 256);
         hipStream_t st = ctx->stream;
@@ -1233,4 +1450,13 @@ extern "C" int kle_mat_create_rw_sumfac(kle_ctx *ctx, kle_mesh *m, kle_mat **out
 {
     KLE_ARG(ctx && m && out, "null arg");
     return sumfac_create(ctx, m, 2, out);
+}
+
+// The no-slip operators of any mesh, sum-factorised: NS_SPECS with
+// k_sumfac_elem<D, LIST, CLS> (Rw, Rwfs: k_sumfac_rw) as the pass
+extern "C" int kle_mat_create_ns_sumfac(kle_ctx *ctx, kle_mesh *m, int which, kle_mat **out)
+{
+    KLE_ARG(ctx && m && out, "null arg");
+    KLE_ARG(which >= 0 && which <= 6, "which must be 0 (K), 1 (Krhs), 2 (Rw), 3 (Kfs), 4 (Krhsfs), 5 (Rwfs) or 6 (K + Kfs)");
+    return sumfac_create(ctx, m, NS_SPECS[which].rw ? 2 : 0, out, which);
 }

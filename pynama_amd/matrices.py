@@ -38,12 +38,12 @@ def kle_op_type(opType=None):
 
 def kle_ns_type(nsType=None):
     """The form of the no-slip KLE matrices (MatNS): the keyword, else
-    -kle_ns_type, else "assembled"; anything but assembled | element raises
-    Error 62."""
+    -kle_ns_type, else "assembled"; anything but assembled | element | sumfac
+    raises Error 62."""
     if nsType is None:
         nsType = Options().getString("kle_ns_type", "assembled")
-    if nsType not in ("assembled", "element"):
-        raise Error(62, f"-kle_ns_type {nsType}: assembled | element")
+    if nsType not in ("assembled", "element", "sumfac"):
+        raise Error(62, f"-kle_ns_type {nsType}: assembled | element | sumfac")
     return nsType
 
 
@@ -203,7 +203,10 @@ class MatNS(MatFS):
         (Mat.createNSElement) and never calls kle_assemble_ns; Rd and Rdfs are
         empty assembled matrices and mat.kle keeps its order of eight.  Uniform
         box meshes, one rank or slabs on several; anything else raises Error
-        56.  This switch is the way to the matrix-free no-slip system:
+        56.  "sumfac" builds the same seven as sum-factorised operators
+        (Mat.createNSSumFactored) on any mesh, Gmsh meshes and their partitions
+        included, sharing one geometry set; with opType="sumfac" as well nothing
+        at all is assembled.  This switch is the way to the matrix-free no-slip system:
         kleType="element" / -kle_mat_type element (and "sumfac") name the
         free-slip forms, which a no-slip mesh does not have, and keep raising
         Error 56 here."""
@@ -221,11 +224,12 @@ class MatNS(MatFS):
     def buildNS(self, nsType="assembled"):
         ctx = get_ctx()
         mesh = self.dom.getMesh()
-        if nsType == "element":
+        if nsType in ("element", "sumfac"):
             # matrix-free: no kle_assemble_ns, no assembled values
             dim = self.dom.getDimensions()[0]
             names = ("K", "Krhs", "Rw", "Kfs", "Krhsfs", "Rwfs", "K+Kfs")
-            ops = {n: Mat.createNSElement(mesh, n) for n in names}
+            create = Mat.createNSElement if nsType == "element" else Mat.createNSSumFactored
+            ops = {n: create(mesh, n) for n in names}
             for n, m in ops.items():
                 m.setName(n)
             self.K, self.Krhs, self.Rw = ops["K"], ops["Krhs"], ops["Rw"]

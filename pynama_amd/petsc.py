@@ -383,6 +383,31 @@ class Mat:
         return m
 
     @classmethod
+    def createNSSumFactored(cls, mesh, which="K"):
+        """Sum-factorised no-slip operator of any mesh, uniform box or
+        unstructured, one rank or the parts of a partition
+        (kle_mat_create_ns_sumfac): K, Krhs, Rw, Kfs, Krhsfs, Rwfs or K+Kfs of
+        MatNS.buildNS with the masks acting per velocity DoF, as
+        createNSElement's, but every product is a quadrature-point evaluation
+        with per-point geometry (createKLESumFactored's kernels with a class
+        table per element node): no assembled values and no element matrix.
+        The seven operators of a mesh share one geometry set.  Same call
+        surface as createNSElement (getDiagonal: K, K+Kfs, Kfs, Krhs, Krhsfs;
+        copyDirichletRows: the identity rows; KSP.setOperators); needs a mesh
+        with its no-slip DoFs set -- a free-slip mesh and a mesh partitioned
+        for another rank count raise Error 56, any other `which` Error 62."""
+        kinds = {"K": 0, "Krhs": 1, "Rw": 2, "Kfs": 3, "Krhsfs": 4, "Rwfs": 5, "K+Kfs": 6}
+        if which not in kinds:
+            raise Error(62, f"createNSSumFactored: which must be one of {', '.join(kinds)}, not {which!r}")
+        ctx = get_ctx()
+        h = C.c_void_p()
+        call("kle_mat_create_ns_sumfac", ctx.h, mesh._h, kinds[which], C.byref(h))
+        dim_w = 1 if mesh.dim == 2 else 3
+        m = cls._wrap(h, ctx, mesh, mesh.dim, dim_w if which in ("Rw", "Rwfs") else mesh.dim)
+        m.setName("sum-factorised " + which)
+        return m
+
+    @classmethod
     def createOperatorElement(cls, mesh, which="Curl"):
         """Element-wise Curl, SrT or DivSrT of a uniform box mesh
         (kle_mat_create_operator_element): sum-factorised products from the

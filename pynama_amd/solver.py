@@ -37,7 +37,8 @@ class KleSolver:
     exactly (Mat.copyDirichletRows).  After a sum-factorised build
     (-kle_mat_type sumfac), whose operators hold no such call, they are held to
     the solve's rtol, as in the assembled solve and as with -kle_k_type
-    sumfac."""
+    sumfac.  The matrix-free no-slip builds (-kle_ns_type element | sumfac)
+    copy the identity rows of K and of K + Kfs back exactly."""
 
     def __init__(self):
         self.mat = None
@@ -69,8 +70,10 @@ class KleSolver:
         # Dirichlet values exactly.  The sum-factorised operators refuse
         # copyDirichletRows, so after a sumfac build the Dirichlet values are
         # held to the solve's rtol, as in the assembled solve and with
-        # -kle_k_type sumfac.
-        self._exactBC = K.getFormat() == "elem" and "k_sumfac" not in K.spmvKernel()
+        # -kle_k_type sumfac.  The sum-factorised no-slip operators
+        # (-kle_ns_type sumfac) copy their identity rows like the element-wise ones.
+        kern = K.spmvKernel() if K.getFormat() == "elem" else ""
+        self._exactBC = K.getFormat() == "elem" and ("k_sumfac" not in kern or "k_sumfac_gather_cls" in kern)
         self.solver = KspSolver()
         self.solver.createSolver(self.mat.getElementK() if ktype == "element"
                                  else self.mat.getSumFactoredK() if ktype == "sumfac" else K)

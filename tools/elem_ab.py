@@ -103,8 +103,27 @@ forms):
 With --check: Taylor-Green with the matrix-free set to rtol 1e-10, the true
 residual K u - (Rw w + Krhs u_bc) formed through the assembled K, Krhs and Rw.
 
+With --sumfac-noslip the legs are those of the matrix-free no-slip system on
+an unstructured mesh (Mat.createNSSumFactored, MatNS.build(nsType="sumfac");
+records to profiles/elem/sumfac_noslip.jsonl), one process, on
+perturbed_box(3, nelem, seed=5) of the first mesh with six no-slip walls:
+
+  build_ns        wall time and device memory (hipMemGetInfo before / after) of
+                  MatNS.build(buildOperators=False) per nsType; where the
+                  assembled set cannot be built the record says so and the legs
+                  against it are left out
+  product_<op>    --reps products of the seven operators, sum-factorised and
+                  assembled, with the algorithmic bytes (spmv_bytes)
+  product_K_cls_vs_node   the class-masked K against the free-slip
+                  sum-factorised K of the same mesh (the per-node mask folded
+                  into the connectivity): the price of the class table
+  solve_ns        one solveFS + solve at rtol 1e-10 with nothing of the KLE
+                  system assembled: iterations, and the true residuals
+                  (K+Kfs) v - bFS and K u - b through the assembled matrices
+
   python tools/elem_ab.py [--meshes 20,16,16:5 8,8,6:7] [--rounds 3] [--check]
-                          [--matfree | --operators [--config4] | --noslip | --sumfac | --sumfac-system]
+                          [--matfree | --operators [--config4] | --noslip | --sumfac | --sumfac-system |
+                           --sumfac-noslip]
 """
 import argparse
 import ctypes as C
@@ -960,6 +979,150 @@ def noslip(a, pa, np, hip, ctx, emit):
               finite=bool(np.all(np.isfinite(vel.getArray())))))
 
 
+def sumfac_noslip(a, pa, np, hip, ctx, emit):
+    import tempfile
+
+    from pynama_amd.meshgen import perturbed_box, write_gmsh
+    from pynama_amd.petsc import Mat
+    ne_s, ngl = a.meshes[0].split(":")
+    nelem, ngl = [int(v) for v in ne_s.split(",")], int(ngl)
+    dim = len(nelem)
+    path = os.path.join(tempfile.mkdtemp(prefix="kle_sumfac_noslip_"), "mesh.msh")
+    write_gmsh(path, dim, *perturbed_box(dim, nelem, seed=5))
+
+    def domain(bc):
+        dom = pa.Domain()
+        dom.configure({"domain": {"ngl": ngl, "gmsh-file": path}, "boundary-conditions": bc})
+        dom.setUp()
+        return dom
+
+    def build(dom, kind):
+        mat = pa.MatNS()
+        mat.setDomain(dom)
+        mat.build(buildOperators=False, nsType=kind)
+        ctx.synchronize()
+        return mat
+
+    dom = domain({"no-slip": NS_WALLS})
+    base = {"mesh": "perturbed_box seed 5", "nelem": nelem, "ngl": ngl, "dofs": dom.mesh.N * dim,
+            "walls": sorted(NS_WALLS), "rounds": a.rounds}
+    kinds = ["sumfac", "assembled"]
+    mats, t_build, mem, refused = {}, {k: [] for k in kinds}, {}, None
+    for rnd in range(a.rounds + 1):  # round 0: untimed (module load, first allocations)
+        for kt in list(kinds):
+            mats.pop(kt, None)
+            gc.collect()
+            ctx.synchronize()
+            m0 = hip.free_bytes()
+            t0 = time.perf_counter()
+            try:
+                mats[kt] = build(dom, kt)
+            except pa.Error as e:
+                if kt != "assembled":
+                    raise
+                refused = {"error": str(e), "free_bytes_before": m0}
+                kinds.remove(kt)
+                gc.collect()
+                continue
+            t1 = time.perf_counter()
+            if rnd:
+                t_build[kt].append(1e3 * (t1 - t0))
+                mem[kt] = m0 - hip.free_bytes()
+    for kt in kinds:
+        emit(dict(base, leg="build_ns", nsType=kt, formats=[m.getFormat() for m in mats[kt].kle],
+                  ms=spread(t_build[kt]), device_memory={"bytes_kle_and_Ksum": mem[kt]}))
+    if refused:
+        emit(dict(base, leg="build_ns", nsType="assembled", fits=False, **refused))
+    else:
+        emit(dict(base, leg="ratio_build_ns", assembled_over_sumfac={
+            "build": statistics.median(t_build["assembled"]) / statistics.median(t_build["sumfac"]),
+            "device_memory": mem["assembled"] / max(mem["sumfac"], 1)}))
+
+    def get(mat, nm):
+        return mat.getKplusKfs() if nm == "K+Kfs" else getattr(mat, nm)
+
+    def time_legs(ops, x, y):
+        t = {k: [] for k in ops}
+        for _ in range(a.rounds):
+            for label, A in ops.items():
+                for _w in range(20):
+                    A.mult(x, y)
+                ms = hip.timed_ms(lambda: [A.mult(x, y) for _r in range(a.reps)])
+                t[label].append(1e3 * ms / a.reps)
+        return t
+
+    for nm in ("K", "Krhs", "Rw", "Kfs", "Krhsfs", "Rwfs", "K+Kfs"):
+        ops = {kt: get(mats[kt], nm) for kt in kinds}
+        x = ops["sumfac"].createVecRight()
+        x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+        y = ops["sumfac"].createVecLeft()
+        t = time_legs(ops, x, y)
+        for label, A in ops.items():
+            emit(dict(base, leg="product_" + nm, operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                      reps=a.reps, us=spread(t[label]),
+                      tb_per_s=A.spmvBytes() / statistics.median(t[label]) * 1e-6))
+        if "assembled" in t:
+            emit(dict(base, leg="ratio_" + nm, assembled_over_sumfac=statistics.median(t["assembled"]) /
+                      statistics.median(t["sumfac"]),
+                      differ_beyond_spread=bool(max(t["sumfac"]) < min(t["assembled"]) or
+                                                max(t["assembled"]) < min(t["sumfac"]))))
+    # the class table: the masked K against the free-slip K of the same mesh (per-node mask in the connectivity)
+    fs = domain({"custom-func": {"name": "taylor_green3d" if dim == 3 else "taylor_green"}})
+    ops = {"per_dof_class": mats["sumfac"].K, "per_node": Mat.createKLESumFactored(fs.mesh, "K")}
+    x = ops["per_dof_class"].createVecRight()
+    x.setArray(np.random.default_rng(1).uniform(-1, 1, x.getLocalSize()))
+    y = ops["per_dof_class"].createVecLeft()
+    t = time_legs(ops, x, y)
+    for label, A in ops.items():
+        emit(dict(base, leg="product_K_cls_vs_node", operator=label, kernel=A.spmvKernel(), bytes=A.spmvBytes(),
+                  reps=a.reps, us=spread(t[label])))
+    bc, bn = ops["per_dof_class"].spmvBytes(), ops["per_node"].spmvBytes()
+    emit(dict(base, leg="ratio_K_cls_vs_node", per_dof_class_over_per_node=statistics.median(t["per_dof_class"]) /
+              statistics.median(t["per_node"]), bytes_ratio=bc / bn, class_table_share_of_bytes=(bc - bn) / bc,
+              differ_beyond_spread=bool(max(t["per_node"]) < min(t["per_dof_class"]) or
+                                        max(t["per_dof_class"]) < min(t["per_node"]))))
+    del ops, fs
+    gc.collect()
+    # one solveFS + solve with nothing of the KLE system assembled; true residuals through the assembled matrices
+    mat = mats["sumfac"]
+    sol = pa.KleSolver()
+    sol.setMat(mat)
+    sol.setUp()
+    vort = mat.Rw.createVecRight()
+    vort.setArray(np.random.default_rng(3).uniform(-1, 1, vort.getLocalSize()))
+    vel = sol.getSolution()
+    dom.applyBoundaryConditions(vel, "velocity", 0.0, 0.02)
+    asm = mats.get("assembled")
+    true = {}
+    if asm is not None:  # the right-hand sides before the solves overwrite vel's free entries
+        bfs = asm.Rw * vort
+        bfs.axpy(1.0, asm.Rwfs * vort)
+        bfs.axpy(1.0, asm.Krhsfs * vel)
+        b = asm.Rw * vort
+        b.axpy(1.0, asm.Krhs * vel)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    sol.solveFS(vort)
+    ctx.synchronize()
+    t1 = time.perf_counter()
+    sol.solve(vort)
+    ctx.synchronize()
+    t2 = time.perf_counter()
+    if asm is not None:
+        r = asm.getKplusKfs() * sol.getFreeSlipSolution()
+        r.aypx(-1.0, bfs)
+        true["solveFS"] = r.norm() / bfs.norm()
+        r = asm.K * vel
+        r.aypx(-1.0, b)
+        true["solve"] = r.norm() / b.norm()
+    emit(dict(base, leg="solve_ns", nsType="sumfac", ksp="cg + jacobi", rtol=1e-10,
+              solveFS={"wall_ms": 1e3 * (t1 - t0), "iterations": sol.solverFS.getIterationNumber(),
+                       "reason": sol.solverFS.getConvergedReason(), "operator": mat.getKplusKfs().spmvKernel()},
+              solve={"wall_ms": 1e3 * (t2 - t1), "iterations": sol.getKSP().getIterationNumber(),
+                     "reason": sol.getKSP().getConvergedReason(), "operator": mat.K.spmvKernel()},
+              true_rel_residual_assembled=true or None, finite=bool(np.all(np.isfinite(vel.getArray())))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", nargs="+", default=["20,16,16:5", "8,8,6:7"], help="nelem:ngl")
@@ -981,13 +1144,17 @@ def main():
     ap.add_argument("--sumfac-system", action="store_true",
                     help="the whole matrix-free set (K, Krhs, Rw, Curl, SrT, DivSrT) on the first mesh as an "
                          "unstructured mesh and as a box: builds, products, the evalRHS chain, one evalRHS")
+    ap.add_argument("--sumfac-noslip", action="store_true",
+                    help="the matrix-free no-slip set (K, Krhs, Rw, Kfs, Krhsfs, Rwfs, K+Kfs) on the first mesh as "
+                         "an unstructured six-wall mesh: builds, products, the class table's price, solveFS + solve")
     ap.add_argument("--fallback-meshes", nargs="*", default=["16,12,12:5", "12,10,10:5", "8,8,6:5"],
                     help="with --noslip: tried in order where the assembled no-slip set cannot be built")
     ap.add_argument("--out", default=None, help="default profiles/elem/elem_ab.jsonl (matfree.jsonl with --matfree, "
                                                 "operators.jsonl with --operators, noslip.jsonl with --noslip)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "elem", "sumfac_system.jsonl" if a.sumfac_system else
+        a.out = os.path.join(ROOT, "profiles", "elem", "sumfac_noslip.jsonl" if a.sumfac_noslip else
+                             "sumfac_system.jsonl" if a.sumfac_system else
                              "sumfac.jsonl" if a.sumfac else "noslip.jsonl" if a.noslip else
                              "operators.jsonl" if a.operators else
                              "matfree.jsonl" if a.matfree else "elem_ab.jsonl")
@@ -1005,6 +1172,10 @@ def main():
         fout.write(line + "\n")
         fout.flush()
 
+    if a.sumfac_noslip:
+        sumfac_noslip(a, pa, np, hip, ctx, emit)
+        fout.close()
+        return
     if a.sumfac_system:
         sumfac_system(a, pa, np, hip, ctx, emit)
         fout.close()
